@@ -8,7 +8,20 @@ value = trajectory-iterations/s over all ranks (sum of per-element inner iterati
 time).  N GPUs: one process per GPU, disjoint shards (weak scaling), no collective on the data
 path; a final RCCL gather of per-element summaries to rank 0 after the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set up, W warm-up steps, the K timed
+steps (`ms_per_step` = the time of one of them), the result line.  `--full` adds the legs that take
+time of their own beside it: the CPU baseline (`cpu_baseline`), config C5's full solves in both
+precisions (`extra.full_solve`, with `--riccati-fp32` / `--config c5`) and config C1's CPU solve of
+the same problem (`--config c1`).
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last step as
+`DIR/<name>.npy` (float32 / float64, under 64 MB in all): every element's summary
+(`info_<field>`), the command blocks of the first 4096 elements — the first knots' controls, desired
+body state and feedback gains a caller of the solver publishes (`cmd_<field>`) — and the nominal
+trajectory `Xbar`, `Ubar` of a fixed, seeded sample of 256 elements (`sample_elements`).  The inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 `--gpus N` with N > 1 outside a torch.distributed launch starts the N ranks itself (a child
 `torch.distributed.run`, before this process touches the GPU) and exits with its status.
@@ -93,6 +106,35 @@ def cpu_baseline(args):
                       f"{threads} threads, {dt:.1f} s wall"}
 
 
+DUMP_SAMPLE, DUMP_SEED, DUMP_COMMANDS = 256, 20240807, 4096  # --dump-outputs: elements kept of the large arrays
+
+
+def dump_outputs(path: str, solver, info: dict, cmds: np.ndarray) -> None:
+    """--dump-outputs: the state the last timed step left, as a caller of the path receives it
+    (hsddp_download_element_info, hsddp_extract_commands, hsddp_download_trajectory), one .npy per
+    array in float32 / float64.  At the metric config: 0.3 MB of summaries, 32 MB of command blocks,
+    20 MB of sampled trajectories."""
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a):
+        a = np.asarray(a)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64))
+
+    for f, v in info.items():
+        save("info_" + f, v)
+    for f in cmds.dtype.names:
+        save("cmd_" + f, cmds[f][:DUMP_COMMANDS])
+    B = solver.B
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=min(B, DUMP_SAMPLE), replace=False))
+    # the nominal trajectory without K (hsddp_download_trajectory takes NULL for it): the dense gains
+    # of the whole batch are 3.8 GB, and the command blocks carry the first knots' feedback
+    Xbar = np.empty((B, solver.S, 24)); Ubar = np.empty((B, solver.Kc, 24))
+    hsddp.check(hsddp.lib().hsddp_download_trajectory(solver._h, hsddp.dp(Xbar), hsddp.dp(Ubar), None))
+    save("sample_elements", idx)
+    save("Xbar", Xbar[idx])
+    save("Ubar", Ubar[idx])
+
+
 def full_solve_c5(prob, device) -> dict:
     """Config C5's other half (BASELINE.json: "fp32 Riccati + ReB/AL outer loop, ... tolerance vs
     fp64 reference reported"): one full MultiPhaseDDP::solve of the same batch with the shipped
@@ -172,30 +214,37 @@ def latency_c1(args) -> None:
             times.append((t1 - t0) * 1e3)
             iters.append(int(solver.element_info()["iters"][0]))
     info = solver.element_info()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver, info, solver.extract_commands())
     solver.close()
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import oracle_lib as O
-    reps = max(5, args.steps)
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        r = O.solve_batch(prob, O.default_options(), n_threads=1)
-    cpu_ms = (time.perf_counter() - t0) / reps * 1e3
-    model, nproc, affinity = host_cpu()
     ms = float(np.median(times))
+    extra = {"ms_min": float(np.min(times)), "ms_max": float(np.max(times)), "inner_iterations": iters[0],
+             "us_per_inner_iteration": ms * 1e3 / max(1, iters[0])}
+    cpu = None
+    if args.full:  # the oracle's solve of the same problem: the CPU figure and the comparison
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import oracle_lib as O
+        reps = max(5, args.steps)
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            r = O.solve_batch(prob, O.default_options(), n_threads=1)
+        cpu_ms = (time.perf_counter() - t0) / reps * 1e3
+        model, nproc, affinity = host_cpu()
+        extra.update(iterations_equal_oracle=bool(iters[0] == int(r["iters"][0])),
+                     cost_rel_diff_vs_oracle=float(abs(info["cost"][0] - r["cost"][0]) / abs(r["cost"][0])))
+        cpu = {"value": cpu_ms, "unit": "ms/solve", "cores": 1, "kind": "port",
+               "host": {"cpu_model": model, "nproc": nproc, "affinity_cpus": affinity},
+               "sample": f"oracle/hsddp_oracle.c (-O2, fp64), the same problem and options, "
+                         f"{reps} solves on one thread"}
     out = {"metric": "full solve latency, 1-phase 50-knot HKD trot, batch=1 (BASELINE config 1)", "value": ms,
            "unit": "ms/solve", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
            "higher_is_better": False, "scaling": "none", "vs_baseline": None, "dtype": "f64",
            "data": "synthetic: seeded random initial state (splitmix64), closed-form trot reference (SURVEY.md §8d)",
            "config": {"workload": "HKD trot, 1 phase x 50 knots, batch=1 (BASELINE config 1), ddp_setting.info "
                                   "(max_AL_iter 5, max_DDP_iter 10, early exits)", "global_batch": 1},
-           "extra": {"ms_min": float(np.min(times)), "ms_max": float(np.max(times)), "inner_iterations": iters[0],
-                     "iterations_equal_oracle": bool(iters[0] == int(r["iters"][0])),
-                     "cost_rel_diff_vs_oracle": float(abs(info["cost"][0] - r["cost"][0]) / abs(r["cost"][0])),
-                     "us_per_inner_iteration": ms * 1e3 / max(1, iters[0])},
-           "cpu_baseline": {"value": cpu_ms, "unit": "ms/solve", "cores": 1, "kind": "port",
-                            "host": {"cpu_model": model, "nproc": nproc, "affinity_cpus": affinity},
-                            "sample": f"oracle/hsddp_oracle.c (-O2, fp64), the same problem and options, "
-                                      f"{reps} solves on one thread"}}
+           "extra": extra}
+    if cpu is not None:
+        out["cpu_baseline"] = cpu
     print(json.dumps(out), flush=True)
 
 
@@ -230,7 +279,12 @@ def main():
     ap.add_argument("--cpu-elements", type=int, default=2048)
     ap.add_argument("--cpu-iters", type=int, default=10)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core of this process's share")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the CPU baseline, config C5's full "
+                         "solves in both precisions, config C1's CPU solve of the same problem")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0's shard)")
     ap.add_argument("--riccati-fp32", action="store_true",
                     help="config C5: fp32 LQ records / Riccati sweep / linear rollout (fp64 rollout, costs, outer loop)")
     ap.add_argument("--config", default="metric", choices=["metric", "c1", "c2", "c3", "c4", "c5"],
@@ -377,9 +431,11 @@ def main():
                       "final_gather": gather,
                       "all_costs_finite": finite, "device_bytes": solver.device_bytes()},
         }
-        if world == 1 and not args.no_cpu_baseline and not args.riccati_fp32 and not args.mixed:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, solver, info, np.frombuffer(cmd.cpu().numpy().tobytes(), dtype=hsddp.MPC_COMMAND))
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.riccati_fp32 and not args.mixed:
             out["cpu_baseline"] = cpu_baseline(args)
-        if world == 1 and args.riccati_fp32:
+        if args.full and world == 1 and args.riccati_fp32:
             out["extra"]["full_solve"] = full_solve_c5(prob, local)
         print(json.dumps(out), flush=True)
     solver.close()

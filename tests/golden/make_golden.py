@@ -88,5 +88,41 @@ def main():
     print("wrote", out, os.path.getsize(out), "bytes")
 
 
+LIVE_SEED, LIVE_POINTS = 77, 50
+
+
+def live_points():
+    """The seeded points of tests/test_oracle_model.py::test_live_against_reference_kernels."""
+    rng = np.random.default_rng(LIVE_SEED)
+    pts = []
+    for _ in range(LIVE_POINTS):
+        x = rng.uniform(-0.7, 0.7, 24); x[5] = rng.uniform(0.1, 0.4)
+        u = rng.uniform(-50, 50, 24); c = rng.integers(0, 2, 4).astype(float)
+        pts.append((x, u, c))
+    return pts
+
+
+def evaluate_reference(R, pts, dt=0.01):
+    """hkinodyn and hkinodyn_par of the reference kernels at pts: xn [n][24], A, B [n][576] (CasADi column-major)."""
+    xn = np.zeros((len(pts), 24)); A = np.zeros((len(pts), 576)); B = np.zeros((len(pts), 576))
+    for q, (x, u, c) in enumerate(pts):
+        R.ref_hkinodyn(dp(x), dp(u), dt, dp(c), dp(xn[q]))
+        R.ref_hkinodyn_par(dp(x), dp(u), dt, dp(c), dp(A[q]), dp(B[q]))
+    return xn, A, B
+
+
+def live_fixture():
+    """tests/golden/hkd_model_points77.npz: the reference kernels' outputs at live_points(), so the
+    test that used to need oracle/_ref runs from stored vectors where the reference is absent."""
+    R = O.ref_lib()
+    if R is None:
+        raise SystemExit("oracle/_ref not built (needs the reference's sources): make -C oracle ref")
+    xn, A, B = evaluate_reference(R, live_points())
+    out = os.path.join(HERE, "hkd_model_points77.npz")
+    np.savez_compressed(out, xn=xn, A=A, B=B)
+    print("wrote", out, os.path.getsize(out), "bytes")
+
+
 if __name__ == "__main__":
     main()
+    live_fixture()

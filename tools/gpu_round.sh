@@ -22,7 +22,7 @@ if [ "$MODE" = all ] || [ "$MODE" = tests ]; then
     step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-    step bench 600 python bench.py
+    step bench 600 python bench.py --full
 fi
 if [ "$MODE" = all ] || [ "$MODE" = prof ]; then
     cd /tmp && export TMPDIR=/tmp
@@ -35,7 +35,7 @@ if [ "$MODE" = all ] || [ "$MODE" = pmc ]; then
 fi
 # config C5: fp32 Riccati mode — bench line, tolerance against fp64, kernel trace and PMC traffic
 if [ "$MODE" = all ] || [ "$MODE" = fp32 ]; then
-    step bench_fp32 300 python bench.py --riccati-fp32
+    step bench_fp32 300 python bench.py --full --riccati-fp32
     step fp32_tolerance 600 python -u tools/fp32_tolerance.py
     cd /tmp && export TMPDIR=/tmp
     step rocprof_trace_fp32 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_trace_fp32" -o run -- \
