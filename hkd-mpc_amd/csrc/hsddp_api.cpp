@@ -785,9 +785,10 @@ extern "C" int hsddp_update_problem(hsddp_handle h, const int *contacts, const d
 
 // params (a new problem: hsddp_upload_warm_start): the working trajectory restarts at the warm
 // start (X = Xbar, U = Ubar, Defect = 0), the ReB / AL parameters and touchdown constraints return
-// to their initial values and the constraint values to zero — else all of them are kept.  Either
-// way dX = du = dU = 0 (the next initial rollout multiplies them by eps = 0), the per-element solver
-// state is cleared and pending touchdown masks are resolved from the contact rows.
+// to their initial values and the constraint values to zero — else all of them are kept.  A new
+// problem zeroes dX, du and dU; an update keeps them, except that dX is zeroed under single
+// shooting (the reasons stand at the memsets below).  Either way the per-element solver state is
+// cleared and pending touchdown masks are resolved from the contact rows.
 static int reset_working(hsddp_handle h, bool params)
 {
     const Params &p = h->p;

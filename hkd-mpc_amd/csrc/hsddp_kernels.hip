@@ -25,10 +25,6 @@ namespace hsddp {
 
 using namespace hkd;
 
-#ifndef HSDDP_RO_EXP
-#define HSDDP_RO_EXP 0  // timing experiments only: 1 no Defect row stores, 2 no trial U row stores (k_rollout),
-                        // 3 no running cost, 4 running cost without reference loads, 5 no control-row loads or stores
-#endif
 #ifndef HSDDP_STAMPS
 #define HSDDP_STAMPS 0
 #endif
@@ -49,9 +45,6 @@ using namespace hkd;
 #define RSTAMP(n) \
     do {          \
     } while (0)
-#endif
-#ifndef HSDDP_LQ_EXP
-#define HSDDP_LQ_EXP 0  // timing experiment only: 1 no terminal tasks
 #endif
 #ifndef FWD_MINB
 #define FWD_MINB 2  // 256-thread blocks per CU for the knot-parallel kernels (k_lq, k_rollout)
@@ -164,10 +157,7 @@ DEV void terminal_task(const Params &p, const Bufs &d, TermLds &S, int task, int
         sincos(a, &strig[2 * t], &strig[2 * t + 1]);
     }
     wave_sync();
-#ifndef HSDDP_TERM_EXP
-#define HSDDP_TERM_EXP 0
-#endif
-    if ((HSDDP_TERM_EXP & 2) == 0 && t < 4) {
+    if (t < 4) {
         // legs of the touchdown constraints: foot height h and its gradient (non-zeros at 0..2, 5,
         // 12 + 3 l + k); legs touching down at a phase boundary: the reset map's foot-Jacobian rows
         // — from one evaluation of the leg's kinematics (hkd_foot_height_grad_sparse's and
@@ -231,11 +221,11 @@ DEV void terminal_task(const Params &p, const Bufs &d, TermLds &S, int task, int
     wave_sync();
     KParams &kp = *kparams();  // runtime-indexed weights
     double *rec = d.term + ((size_t)b * p.P + i) * TW;
-    if ((HSDDP_TERM_EXP & 1) == 0 && t == 0) {  // the phase's terminal cost at X[N] (SinglePhase::compute_cost's last term) for k_lq's slot sums
+    if (t == 0) {  // the phase's terminal cost at X[N] (SinglePhase::compute_cost's last term) for k_lq's slot sums
         double tv;
         d.slot_cost[(size_t)b * p.S + s] = terminal_cost_h(p, sc, sx, sxr, spf, smask, ssl, ssl + MTD * 4, sh, tv);
     }
-    if ((HSDDP_TERM_EXP & 8) == 0 && t < NX) { // Phix
+    if (t < NX) { // Phix
         const int j = t;
         double v = kp.qf_gain * kp.qf_scale[j] * q_diag(kp, sc, j) * (sx[j] - sxr[j]);
         if (j >= 3 && j < 6) {
@@ -277,7 +267,7 @@ DEV void terminal_task(const Params &p, const Bufs &d, TermLds &S, int task, int
 #pragma unroll
     for (int l = 0; l < 4; ++l) use[l] = scoef[l][1] != 0.0;
     int r = t / NX, cidx = t % NX;  // entry e = t + TERM_TL j: (r, cidx) advance per step
-    for (int e = t; e < ((HSDDP_TERM_EXP & 4) ? 0 : NN); e += TERM_TL) { // Phixx
+    for (int e = t; e < NN; e += TERM_TL) { // Phixx
         double v = 0.0;
         if (r == cidx)
             v = sdd[r];
@@ -352,9 +342,6 @@ DEV void terminal_wave(const Params &p, const Bufs &d, TermLds *S, long wave, in
     if (wave == 0)
         for (int t = lane; t < LS_LIVE; t += 64) d.ls_live[t] = 0;
     if (wave == 0 && lane < 4) d.counter[lane] = 0;
-#if HSDDP_LQ_EXP == 1
-    return;
-#endif
     const int h = lane / TERM_TL;
     const long task = wave * TERM_TPW + h;
     if (task < (long)p.B * p.P) terminal_task<EL>(p, d, S[h], (int)task, lane % TERM_TL);
@@ -513,11 +500,7 @@ DEV void finish_defect(const Params &p, const Bufs &d, int b, int s, int k, cons
         nrm += xs[j] * xs[j];
         const double df = xs[j] - x[j];
         fs += df * df;
-#if HSDDP_RO_EXP == 1
-        if (df == 12345.678) Dg[j] = df;
-#else
         Dg[j] = df;
-#endif
     }
     d.slot_feas[sb + s] = fs;
     d.slot_div[sb + s] = (k > 0 && sqrt(nrm) > 1e6) ? 1 : 0;
@@ -548,63 +531,16 @@ DEV void finish_running(const Params &p, const Bufs &d, int b, int s, int kc, co
 {
     if constexpr (COLS) {
         const double *dl = d.reb_delta + ((size_t)b * p.Kc + kc) * 20, *ep = d.reb_eps + ((size_t)b * p.Kc + kc) * 20;
-#if HSDDP_RO_STAGED
-        // the reference in two pieces, so that the 60 values are never live at once: the control
-        // reference first (the ReB term, which needs none, covers its loads), then the state and
-        // foot references
-        typedef double d2 __attribute__((ext_vector_type(2)));
-        const size_t r = (size_t)(p.ref_per_element ? b : 0) * p.S + s, w = d.ref_tw;
-        const d2 *col = (const d2 *)d.ref_t + r;
-        double lu, mk, rc;
-        {
-            d2 v[NU / 2];
-#pragma unroll
-            for (int j = 0; j < NU / 2; ++j) v[j] = col[(NX / 2 + j) * w];
-            rc = cost_reb(p, c, u, dl, ep, mk, nullptr);
-            double urv[NU];
-#pragma unroll
-            for (int j = 0; j < NU / 2; ++j) { urv[2 * j] = v[j].x; urv[2 * j + 1] = v[j].y; }
-            lu = cost_control(p, u, urv);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        double lt, lf;
-        {
-            d2 v[(NX + 12) / 2];
-#pragma unroll
-            for (int j = 0; j < NX / 2; ++j) v[j] = col[j * w];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) v[NX / 2 + j] = col[((NX + NU) / 2 + j) * w];
-            double xrv[NX], pfv[12];
-#pragma unroll
-            for (int j = 0; j < NX / 2; ++j) { xrv[2 * j] = v[j].x; xrv[2 * j + 1] = v[j].y; }
-#pragma unroll
-            for (int j = 0; j < 6; ++j) { pfv[2 * j] = v[NX / 2 + j].x; pfv[2 * j + 1] = v[NX / 2 + j].y; }
-            lt = cost_tracking(p, c, x, xrv);
-            lf = cost_foot(p, c, x, xrv, pfv);
-        }
-        d.slot_cost[(size_t)b * p.S + s] = cost_combine(p, c, lt, lu, lf, rc);
-        d.slot_viol[(size_t)b * p.S + s] = mk;
-#else
         alignas(16) double xr[NX], ur[NU], pf[12];
         ref_from_cols(p, d, b, s, xr, ur, pf);
         double viol;
         d.slot_cost[(size_t)b * p.S + s] = running_cost(p, c, x, u, xr, ur, pf, dl, ep, viol);
         d.slot_viol[(size_t)b * p.S + s] = viol;
-#endif
         return;
     }
     const size_t sb = (size_t)b * p.S;
-#if HSDDP_RO_EXP == 3
-    d.slot_cost[sb + s] = x[0];  // timing only: no running cost
-    d.slot_viol[sb + s] = u[0];
-    return;
-#endif
-#if HSDDP_RO_EXP == 4
-    const double *xr = x, *pf = x + 12, *ur = u;  // timing only: the cost without its reference loads
-#else
     const double *xr = ref_ptr(p, d.ref_x, b, s, NX), *pf = ref_ptr(p, d.ref_foot, b, s, 12);
     const double *ur = ref_ptr(p, d.ref_u, b, s, NU);
-#endif
     const double *dl = d.reb_delta + ((size_t)b * p.Kc + kc) * 20, *ep = d.reb_eps + ((size_t)b * p.Kc + kc) * 20;
     double viol;
     d.slot_cost[sb + s] = running_cost(p, c, x, u, xr, ur, pf, dl, ep, viol);
@@ -719,18 +655,10 @@ DEV void stage_trial2(double *L, const Bufs &d, long r0, long nrows, int per, do
     }
 }
 
-#ifndef HSDDP_RO_REVERSE
-#define HSDDP_RO_REVERSE 1
-#endif
-#ifndef HSDDP_RO_STAGED
-#define HSDDP_RO_STAGED 1  // the slot waves' reference loaded in two pieces (0: all 30 pairs at once)
-#endif
-#ifndef HSDDP_RO_COLS
-#define HSDDP_RO_COLS 1  // the slot waves' reference reads from Bufs::ref_t (0: from the rows)
-#endif
-
+// waves per SIMD k_rollout's register budget is sized for; measured: 2 (256 VGPRs, no spills)
+// 0.93 ms/step forward vs 3: 1.23, 4: 1.07
 #ifndef HSDDP_ROLLOUT_WAVES
-#define HSDDP_ROLLOUT_WAVES 2  // measured: 2 (256 VGPRs, no spills) 0.93 ms/step forward vs 3: 1.23, 4: 1.07
+#define HSDDP_ROLLOUT_WAVES 2
 #endif
 
 // trial control row r: U = Ubar + eps du, straight from global memory (the wave's 64 rows are one
@@ -810,9 +738,9 @@ DEV void rollout_block(const Params &p, const Bufs &d, double eps, int init, int
         rollout_boundary<EL>(p, d, eps, init, ((long)blockIdx.x - nslot) * 64 + lane);
         return;
     }
-    // (HSDDP_RO_REVERSE: every second trial walks the slot blocks from the batch's end, where the
-    // trial before's last reads of the same rows may still sit in the memory-side cache)
-    const long blk = (HSDDP_RO_REVERSE && tix > 0 && (tix & 1)) ? nslot - 1 - (long)blockIdx.x : (long)blockIdx.x;
+    // (every second trial walks the slot blocks from the batch's end, where the trial before's last
+    // reads of the same rows may still sit in the memory-side cache)
+    const long blk = (tix > 0 && (tix & 1)) ? nslot - 1 - (long)blockIdx.x : (long)blockIdx.x;
 #if HSDDP_STAMPS
     unsigned long long rst[8];
 #endif
@@ -878,11 +806,7 @@ DEV void rollout_block(const Params &p, const Bufs &d, double eps, int init, int
     const double *x = Xt + (gc - xr0) * RS;
     // the trial control row of the slot, U = Ubar + eps du (k < N)
     double u[NU];
-#if HSDDP_RO_EXP == 5
-    for (int j = 0; j < NU; ++j) u[j] = x[j] * eps;  // timing only: no control-row loads
-#else
     trial_row(d, kubuf(nb), kqr, eps, u);
-#endif
 #if HSDDP_STAMPS
     asm volatile("" : "+v"(u[0]), "+v"(u[NU - 1]));
 #endif
@@ -890,12 +814,9 @@ DEV void rollout_block(const Params &p, const Bufs &d, double eps, int init, int
     // the running cost of a control slot (the terminal cost at k = N: the boundary waves)
     if (mine && k < L.N(i)) {
         d2 *ug = (d2 *)(kubuf(tb) + kq * NU);
-#if HSDDP_RO_EXP == 2 || HSDDP_RO_EXP == 5
-        if (u[0] == 12345.678)
-#endif
 #pragma unroll
         for (int j = 0; j < NU / 2; ++j) ug[j] = d2{u[2 * j], u[2 * j + 1]};
-        finish_running<HSDDP_RO_COLS>(p, d, b, s, L.k0(i) + k, c, x, u);
+        finish_running<true>(p, d, b, s, L.k0(i) + k, c, x, u);
     }
     RSTAMP(4);
     // u_prev: the previous slot's control row is the previous lane's (k > 0: slot s - 1 is a

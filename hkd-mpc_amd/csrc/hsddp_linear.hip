@@ -16,15 +16,6 @@ constexpr int HC = 12;  // coupled controls per knot
 #ifndef HSDDP_STAMPS
 #define HSDDP_STAMPS 0
 #endif
-#ifndef HSDDP_LIN_EXP
-#define HSDDP_LIN_EXP 0  // timing experiments only: 1 no dX / du stores, 2 no arithmetic, 3 no decoupled du stores
-#endif
-// the knot images requested with the non-temporal policy: the iteration's last read of K, the
-// records and dU (0.82 -> 0.73 ms on one box; the sweep's image requests, which the linear rollout
-// reads again, stay default: nt there cost the rollout 0.045 ms)
-#ifndef HSDDP_LIN_NT
-#define HSDDP_LIN_NT 1
-#endif
 // Diagnostic build (make stamps): s_memtime at the stage boundaries of a knot, differences summed
 // per stage into LDS and written to Bufs::dbg of the wave's second element (tools/stamps.py)
 #if HSDDP_STAMPS
@@ -233,17 +224,18 @@ struct LinSrc {
 
 // Issued as inline asm so the waitcnt pass does not track the LDS writes (it would otherwise wait
 // for every DMA in flight before any LDS read); lin_knot waits explicitly.  LDS destination of
-// element h's piece 64 j + lane: v[h] + 1024 j + 16 lane.
+// element h's piece 64 j + lane: v[h] + 1024 j + 16 lane.  Requested with the non-temporal policy:
+// this is the iteration's last read of K, the records and dU (0.82 -> 0.73 ms on one box; the
+// sweep's image requests, which the linear rollout reads again, stay default: nt there cost the
+// rollout 0.045 ms).
 template <typename real>
 DEV void lin_fetch(LinBuf<real> &buf, const LinSrc<real> &src)
 {
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int j = 0; j < LinImg<real>::NI; ++j) {
-            if (HSDDP_LIN_NT) lds_dma16_nt(src.p[h][j], (unsigned)(size_t)(buf.v[h] + 1024 * j));
-            else lds_dma16(src.p[h][j], (unsigned)(size_t)(buf.v[h] + 1024 * j));
-        }
+        for (int j = 0; j < LinImg<real>::NI; ++j)
+            lds_dma16_nt(src.p[h][j], (unsigned)(size_t)(buf.v[h] + 1024 * j));
 }
 
 template <int W>
@@ -328,7 +320,8 @@ struct LinOut {
     real vu, vx;      // the pending knot's values
     int n;            // pending knots (0 or 1)
     int nprev;        // store instructions the previous knot issued after its image requests
-    bool ust;         // this lane stores its du entry
+    bool ust;         // this lane stores its du entry: always true.  Kept as a field because without the
+                      // branch on it k_lin_rollout<float> compiles to other code (SGPR spills to VGPR lanes)
 };
 
 template <typename real>
@@ -343,9 +336,6 @@ DEV void lin_push(LinOut<real> &out, real du, real nx)
 template <typename real>
 DEV int lin_store_pending(bool go, bool st, LinOut<real> &out)
 {
-#if HSDDP_LIN_EXP == 1
-    go = false;
-#endif
     if (!go || out.n == 0) return 0;
     out.n = 0;
     if (st) {
@@ -380,14 +370,6 @@ DEV void lin_knot(const Params &p, LinVec<real> &S, LinBuf<real> &cur, LinBuf<re
     out.nprev = ns;
     LSYNC();
     LSTAMP(1);
-#if HSDDP_LIN_EXP == 2
-    {
-        const real v = ((const real *)cur.v[hf])[r];
-        lin_push(out, v, v);
-        dx = v;
-        return;
-    }
-#endif
     const char *img = cur.v[hf];
     const real *kimg = (const real *)(img + I::K), *lq = (const real *)(img + I::LQ), *dd = (const real *)(img + I::D);
     const double *dUi = (const double *)(img + I::DU);
@@ -551,7 +533,7 @@ __global__ __launch_bounds__(64, 2) void k_lin_rollout(Params p, Bufs d)
         R.cpl = rowl && (rr < HC ? stl : !stl);
         R.krow0 = (rr % HC) * NX;
         lin_row(p, R, r);
-        out.ust = HSDDP_LIN_EXP == 3 ? R.cpl : true;  // (3: timing only, the decoupled du entries not stored)
+        out.ust = true;
         out.du = d.du + (b * p.Kc + k0) * NX + rr;
         out.dx = d.dX + (b * p.S + s0 + 1) * NX + rr;
         real q1s = 0, q2s = 0;

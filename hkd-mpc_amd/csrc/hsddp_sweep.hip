@@ -30,12 +30,15 @@
 //   K = -Quu_cc^-1 Qux_c, dU, G = Qx - Qux_c^T Quu_cc^-1 Qu_c  (the sweep's dV is formed only with
 //   single shooting, DV: with MS the linear rollout replaces it, quirk A3)
 //   H = Qxx - Qux_c^T Quu_cc^-1 Qux_c by DPP broadcast of K from the lanes holding it
-//   (HSDDP_VALUE_MFMA = 1: on the matrix cores, v_mfma_f64_16x16x4_f64, symmetric tiles)
 //   K rows and dU stored after one wait for all vector memory operations (nothing waits on them)
 // Only the 12 coupled controls (those whose B column is non-zero, DESIGN.md §3.1 "Decoupled controls") enter
 // the elimination; the other 12 are decoupled: K row 0, dU = -lu / (dt R + reg), exactly as the
 // reference's dense 24-control solve gives them.  PSD test: every elimination pivot of Quu_cc and
 // every decoupled diagonal must exceed 1e-9 (the reference's LDLT of Quu - 1e-9 I).
+//
+// One knot body, knot<W>, serves both kernels: W = -1 is the one-wave sweep above (k_riccati), W = 0 / 1
+// the two waves of the column split for small batches (k_riccati_cs), which share one element pair
+// and each form half of the columns.
 //
 // Templates on `real`: double (the reference's T = double) and float (config C5's fp32 mode).
 #include "hsddp_wave.h"
@@ -49,19 +52,10 @@ namespace sweep {
 #ifndef HSDDP_STAMPS
 #define HSDDP_STAMPS 0
 #endif
-// value update on the matrix cores (1) or by DPP-broadcast multiply-adds from the lanes holding
-// K_c (0, no LDS round trip)
 // waves per SIMD the two-pair workgroups' register budget is sized for: 1 (their launches have at
 // most one wave per SIMD: the spills go to AGPRs, not scratch)
 #ifndef SWEEP_WPB2_WPE
 #define SWEEP_WPB2_WPE 1
-#endif
-// knot images requested with the non-temporal policy (A/B experiment)
-#ifndef HSDDP_SWEEP_NT
-#define HSDDP_SWEEP_NT 0
-#endif
-#ifndef HSDDP_VALUE_MFMA
-#define HSDDP_VALUE_MFMA 0
 #endif
 // In-kernel stamps (diagnostic build only, make stamps): s_memtime at the stage boundaries of a
 // knot (each after a full LDS drain, so stages do not overlap), differences summed per stage into
@@ -92,7 +86,18 @@ namespace sweep {
         __builtin_amdgcn_sched_barrier(0);   \
     } while (0)
 
-constexpr int HC = 12;        // coupled controls per knot
+// Workgroup barrier of the column split: this wave's LDS writes done, both waves here.  No wait
+// for vector memory (the knot images and the K / dU stores stay in flight: each wave waits for its
+// own requests with vmcnt before the barrier that publishes them).
+#define CSYNC()                                              \
+    do {                                                     \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
+        __builtin_amdgcn_s_barrier();                        \
+        asm volatile("" ::: "memory");                       \
+        __builtin_amdgcn_sched_barrier(0);                   \
+    } while (0)
+
+constexpr int HC = 12;       // coupled controls per knot
 constexpr int MS = 26;        // M / Z / P image row stride (reals): conflict-free rows and columns
 constexpr int TS = 14;        // T / Qux^T / Kp^T image row stride
 constexpr int WS = 25;        // W image row stride (phase boundary)
@@ -241,8 +246,28 @@ DEV void fetch(Lds<real> &S, const real *rec0, const real *def0, const real *rec
             const real *rec = e ? rec1 : rec0, *def = e ? def1 : def0;
             const real *src = q < PC::NA ? rec + PC::E * q : q < PC::NA + PC::ND ? def + PC::E * (q - PC::NA)
                                                                                  : rec + PC::E * (q - PC::ND);
-            if (HSDDP_SWEEP_NT) lds_dma16_nt(src, (unsigned)(size_t)(&S.img[0][0]) + 1024u * t);
-            else lds_dma16(src, (unsigned)(size_t)(&S.img[0][0]) + 1024u * t);
+            lds_dma16(src, (unsigned)(size_t)(&S.img[0][0]) + 1024u * t);
+        }
+    }
+}
+
+// fetch for the column split: wave W requests its half of the two items' pieces into image buffer q
+template <int W, typename real>
+DEV void fetch_cs(LdsCS<real> &S, int q, const real *rec0, const real *def0, const real *rec1, const real *def1,
+                  int lane)
+{
+    using PC = Pieces<real>;
+    constexpr int H = (PC::NI + 1) / 2;
+#pragma unroll
+    for (int u = 0; u < H; ++u) {
+        const int t = W * H + u;
+        const int n = 64 * t + lane;
+        if (t < PC::NI && n < 2 * PC::NP) {
+            const int e = n >= PC::NP, qq = n - e * PC::NP;
+            const real *rec = e ? rec1 : rec0, *def = e ? def1 : def0;
+            const real *src = qq < PC::NA ? rec + PC::E * qq : qq < PC::NA + PC::ND ? def + PC::E * (qq - PC::NA)
+                                                                                    : rec + PC::E * (qq - PC::ND);
+            lds_dma16(src, (unsigned)(size_t)(&S.img[q][0][0]) + 1024u * t);
         }
     }
 }
@@ -402,20 +427,50 @@ DEV void eliminate(real (&w)[HC], real (&w2)[HC], unsigned long long &bad)
 // the coupled controls' part, positions < 12 one decoupled control each.  Without DV (multiple
 // shooting) it is not formed: the linear rollout replaces it (quirk A3), and that instantiation is
 // the one the metric runs.
-template <typename real, bool DV>
-DEV void knot(const Params &p, Lds<real> &S, const Lane &L, const Phase<real> &ph, const Item<real> &it, int kc,
-              real (&h)[NX], real &g, bool &live, bool first, bool more, const real *nrec0, const real *ndef0,
-              const real *nrec1, const real *ndef1, double &dvs)
+//
+// W = -1: the one-wave sweep (k_riccati), every column formed here; ib and par are ignored.
+// W = 0 / 1: wave W of the column split (k_riccati_cs), the same stages with the column-parallel
+// work halved — T's controls 6 W .. 6 W + 5, the columns cs_wave(c) == W of M, Z, Qxx and H — and
+// the per-element chain (Gn, Qux_c, the Quu_cc columns, the elimination, the K broadcast, G) formed
+// whole in both waves, so each wave holds everything it multiplies by.  Three workgroup barriers
+// stand where the one-wave sweep has a stage fence: M / T rows written -> column reads; Z rows
+// written -> Qxx reads; this wave's H columns written (and its share of the next images landed) ->
+// the other wave's H columns read.  ib: the image buffer of this knot (the next knot's go to
+// ib ^ 1); par: which MZ image holds M (the other takes Z).  Both waves run the same branch
+// decisions (live, the PSD test) on equal values.
+template <int W, bool DV, typename real, typename LdsT>
+DEV void knot(const Params &p, LdsT &S, const Lane &L, const Phase<real> &ph, const Item<real> &it, int kc,
+              real (&h)[NX], real &g, bool &live, bool first, bool more, int ib, int par, const real *nrec0,
+              const real *ndef0, const real *nrec1, const real *ndef1, double &dvs)
 {
-    typename Lds<real>::Item &I = S.it[L.e];
-    const real *img = S.img[L.e];
+    constexpr bool CS = W >= 0;
+    constexpr int Q0 = CS ? 6 * W : 0, Q1 = CS ? Q0 + 6 : HC;  // T's controls formed here
+    auto &I = S.it[L.e];
+    // the LDS view: this knot's image, the M rows' image and the Z rows' image
+    // (the split's two images are pointers formed here; the one-wave sweep names its one image at
+    // every use, as its code always did: either kernel's schedule changes with the other's form)
+    const real *img;
+    real *ma = nullptr, *za = nullptr;
+    if constexpr (CS) {
+        img = S.img[ib][L.e];
+        ma = I.MZ[par];
+        za = I.MZ[par ^ 1];
+    } else {
+        img = S.img[L.e];
+    }
+    auto MA = [&]() -> real * { if constexpr (CS) return ma; else return I.MI; };
+    auto ZA = [&]() -> real * { if constexpr (CS) return za; else return I.MI; };
     const int pp = L.pp, pos = L.pos;
     const real dt = (real)p.dt;
-    real reg = it.reg;
-    STAMP(0);
-    // this knot's images: a phase's first knot waits for them here, every other knot's landed before
-    // the previous knot's output stores (end of knot)
-    if (first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const real reg = it.reg;
+    if constexpr (!CS) STAMP(0);
+    // this knot's images: a phase's first knot waits for them here (split: each wave for its own
+    // requests, then both), every other knot's landed before the previous knot's output stores (end
+    // of knot)
+    if (first) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (CS) CSYNC();
+    }
     // coefficient registers: V[16 k + pos] on register k of every DPP row
     real cf[8];
 #pragma unroll
@@ -423,14 +478,14 @@ DEV void knot(const Params &p, Lds<real> &S, const Lane &L, const Phase<real> &p
     real bv[4], bq[4];
 #pragma unroll
     for (int l = 0; l < 4; ++l) { bv[l] = I.pc[l]; bq[l] = I.pc[4 + l]; }
-    STAMP(1);
+    if constexpr (!CS) STAMP(1);
     // ---- Gn = G + H d (SinglePhase.cpp:320), T = H B_c, M = H A (row pp) ----------------------
     // T and Gn read H first; M = H + H S then accumulates over H's registers (H is not read again:
     // the knot ends by forming the new H) from copies of the 9 entries S's rows read
     real t[HC], ga[4] = {g, 0, 0, 0};
 #pragma unroll
     for (int q = 0; q < HC; ++q) t[q] = 0;
-    emit_Bc(t, h[6], h[7], h[8], h + 9, h + 12, bv, bq, cf);
+    emit_Bc<Q0, Q1>(t, h[6], h[7], h[8], h + 9, h + 12, bv, bq, cf);
     static_for<NX>([&](auto C) { vfma<V_D + C>(ga[C & 3], cf, h[C]); });
     const real gn = (ga[0] + ga[1]) + (ga[2] + ga[3]);
     pin(t);
@@ -441,23 +496,24 @@ DEV void knot(const Params &p, Lds<real> &S, const Lane &L, const Phase<real> &p
     for (int j = 9; j < NX; ++j) h9[j] = 0;
     SSYNC();
     real (&m)[NX] = h;
-    emit_SA(m, h9, cf, dt);
+    emit_SA<W>(m, h9, cf, dt);
     pin(t);
     pin(m);
     if (L.row) {
+        static_for<NX>([&](auto C) {
+            if constexpr (cs_mine<W>(C)) MA()[pp * MS + C] = m[C];
+        });
+        if constexpr (W <= 0) MA()[pp * MS + NX] = gn;
 #pragma unroll
-        for (int c = 0; c < NX; ++c) I.MI[pp * MS + c] = m[c];
-        I.MI[pp * MS + NX] = gn;
-#pragma unroll
-        for (int q = 0; q < HC; ++q) I.TI[pp * TS + q] = t[q];
+        for (int q = Q0; q < Q1; ++q) I.TI[pp * TS + q] = t[q];
     }
-    SSYNC();
-    STAMP(2);
+    if constexpr (CS) CSYNC(); else SSYNC();
+    if constexpr (!CS) STAMP(2);
     // ---- column pp of M (position 24: Gn); Z row, Qux_c column, Qu_c ---------------------------
     const int pc = pp < MS - 1 ? pp : MS - 1;
     real mc[NX];
 #pragma unroll
-    for (int j = 0; j < NX; ++j) mc[j] = I.MI[j * MS + pc];
+    for (int j = 0; j < NX; ++j) mc[j] = MA()[j * MS + pc];
     // Qux_c[q][pp] = (B_c^T M)[q][pp] (lux = 0); position 24: Qu_c = lu_c + B_c^T Gn
     real w2[HC];
 #pragma unroll
@@ -467,17 +523,20 @@ DEV void knot(const Params &p, Lds<real> &S, const Lane &L, const Phase<real> &p
         for (int a = 0; a < 3; ++a) w2[3 * l + a] = lcp[a];
     }
     // Z[pp][i] = M[pp][i] + sum_k M[k][pp] S[k][i] (S^T M transposed); position 24: (S^T Gn)[i]
-    emit_SA(m, mc, cf, dt);
+    emit_SA<W>(m, mc, cf, dt);
     emit_Bc(w2, mc[6], mc[7], mc[8], mc + 9, mc + 12, bv, bq, cf);
     pin(m);
     pin(w2);
-    STAMP(3);
+    if constexpr (!CS) STAMP(3);
     // ---- Qxx = lxx + reg I + (Z + Z^T) / 2 (SinglePhase.cpp:323-352) ---------------------------
     if (pp <= NX) {  // Z rows (two zero columns: the column reads of positions > 24 see zeros)
 #pragma unroll
-        for (int c = 0; c < NX; ++c) I.MI[pp * MS + c] = m[c];
-        I.MI[pp * MS + NX] = 0;
-        I.MI[pp * MS + NX + 1] = 0;
+        for (int c = 0; c < NX; ++c)
+            if (cs_mine<W>(c)) ZA()[pp * MS + c] = m[c];
+        if constexpr (W <= 0) {
+            ZA()[pp * MS + NX] = 0;
+            ZA()[pp * MS + NX + 1] = 0;
+        }
     }
     SSYNC();
     // lxx + reg I into the Z image: each row lane adds its diagonal and lxx cross terms to its own
@@ -485,32 +544,46 @@ DEV void knot(const Params &p, Lds<real> &S, const Lane &L, const Phase<real> &p
     // no read-back round trip; no two lanes touch one entry; the add is the IEEE add of the value
     // stored, as a read-add-write would form it)
     if (L.row) {
-        real *zr = I.MI + pp * MS;
-        lds_add(zr + pp, ph.lxd + reg);
+        real *zr = ZA() + pp * MS;
+        if (cs_mine<W>(pp)) lds_add(zr + pp, ph.lxd + reg);
 #pragma unroll
-        for (int t2 = 0; t2 < 4; ++t2)
-            if ((ph.xmask >> t2) & 1) lds_add(zr + (L.xkind == 1 ? L.xc0 + 3 * t2 : L.xc0), -ph.xw);
+        for (int t2 = 0; t2 < 4; ++t2) {
+            const int xc = L.xkind == 1 ? L.xc0 + 3 * t2 : L.xc0;
+            if (((ph.xmask >> t2) & 1) && cs_mine<W>(xc)) lds_add(zr + xc, -ph.xw);
+        }
     }
-    SSYNC();
-    const real *zrow = L.row ? I.MI + pp * MS : S.zero;
+    if constexpr (CS) CSYNC(); else SSYNC();
+    const real *zrow = L.row ? ZA() + pp * MS : S.zero;
     real qxx[NX], zc[NX];
+    if constexpr (CS) {
+        static_for<NX>([&](auto C) {
+            if constexpr (cs_mine<W>(C)) {
+                qxx[C] = zrow[C];
+                zc[C] = ZA()[C * MS + pc];
+            }
+        });
+        static_for<NX>([&](auto C) {
+            if constexpr (cs_mine<W>(C)) qxx[C] = __builtin_fma(zc[C], (real)0.5, qxx[C] * (real)0.5);
+        });
+    } else {  // (tuned for the one-wave kernel: DESIGN.md §3.1 "Round 3 kept")
 #pragma unroll
-    for (int c = 0; c < NX; ++c) qxx[c] = zrow[c];
+        for (int c = 0; c < NX; ++c) qxx[c] = zrow[c];
 #pragma unroll
-    for (int c = 0; c < NX; ++c) zc[c] = I.MI[c * MS + pc];
-    // every row and column read in flight before the first use (one wait, not one per register reuse)
-    pin(qxx);
-    pin(zc);
+        for (int c = 0; c < NX; ++c) zc[c] = ZA()[c * MS + pc];
+        // every row and column read in flight before the first use (one wait, not one per register reuse)
+        pin(qxx);
+        pin(zc);
 #pragma unroll
-    for (int c = 0; c < NX; ++c) qxx[c] *= (real)0.5;
-    // (r + c) / 2 as r / 2 + c / 2: halving is exact, so the same value, without an add -> multiply
-    // dependence per entry
+        for (int c = 0; c < NX; ++c) qxx[c] *= (real)0.5;
+        // (r + c) / 2 as r / 2 + c / 2: halving is exact, so the same value, without an add -> multiply
+        // dependence per entry
 #pragma unroll
-    for (int c = 0; c < NX; ++c) qxx[c] = __builtin_fma(zc[c], (real)0.5, qxx[c]);
-    pin(qxx);  // materialised here, not sunk to the value update (twice the registers across the elimination)
+        for (int c = 0; c < NX; ++c) qxx[c] = __builtin_fma(zc[c], (real)0.5, qxx[c]);
+        pin(qxx);  // materialised here, not sunk to the value update (twice the registers across the elimination)
+    }
     // Qx = lx + A^T Gn = lx + Gn + S^T Gn
-    const real qx = img[V_LX + (L.row ? pp : 0)] + (gn + I.MI[NX * MS + pc]);
-    STAMP(4);
+    const real qx = img[V_LX + (L.row ? pp : 0)] + (gn + ZA()[NX * MS + pc]);
+    if constexpr (!CS) STAMP(4);
     // ---- Quu_cc column pos = luu + reg + B_c^T T[:, pos] (SinglePhase.cpp:324, MultiPhaseDDP.cpp:160)
     real tcol[18];
 #pragma unroll
@@ -530,9 +603,13 @@ DEV void knot(const Params &p, Lds<real> &S, const Lane &L, const Phase<real> &p
     const int du_z = ((ph.cmask >> ((zl ? pp : 0) / 3)) & 1) ? 12 + pp : pp;  // the decoupled control of pp < 12
     const real quz = img[zl ? V_LU + du_z : V_LU];
     const real qzz = ph.dtrz + reg;
-    // the images are read: the next knot's are requested now (in flight during the elimination)
-    if (more) fetch(S, nrec0, ndef0, nrec1, ndef1, L.lane);
-    STAMP(5);
+    // the images are read: the next knot's are requested now (in flight during the elimination;
+    // split: into the other buffer, read last in the previous knot, before its last barrier)
+    if (more) {
+        if constexpr (CS) fetch_cs<W>(S, ib ^ 1, nrec0, ndef0, nrec1, ndef1, L.lane);
+        else fetch(S, nrec0, ndef0, nrec1, ndef1, L.lane);
+    }
+    if constexpr (!CS) STAMP(5);
     // ---- PSD test + Gauss-Jordan on [Quu_cc | Qux_c | Qu_c] --------------------------------------
     // Qux_c column pp, kept for G and the value update (positions >= 24: zero, so their H row stays 0;
     // DV: position 24 keeps Qu_c for the knot's Qu_c^T dU_c, and its H row is cleared after the update)
@@ -547,81 +624,13 @@ DEV void knot(const Params &p, Lds<real> &S, const Lane &L, const Phase<real> &p
     const bool okh = L.e ? (bad >> 32) == 0 : (bad & 0xffffffffull) == 0;
     live = live && okh;
     const bool st = live;  // this half writes the knot's outputs
-    STAMP(6);
-    // ---- outputs: dU through LDS (K_c rows and dU go out at the end of the knot) ---------------------
+    if constexpr (!CS) STAMP(6);
+    // ---- outputs: dU through LDS (K_c rows and dU go out at the end of the knot; split: both waves
+    // write the same values) ---------------------------------------------------------------------
     if (pp == NX)  // coupled dU from position 24
 #pragma unroll
         for (int q = 0; q < HC; ++q) I.du[(((ph.cmask >> (q / 3)) & 1) ? 0 : 12) + q] = w2[q];
     if (zl) I.du[du_z] = -(quz / qzz);
-#if HSDDP_VALUE_MFMA
-    // K_c^T rows (row 24: dU_c) and Qux_c^T rows for the value update
-    if (pp <= NX)
-#pragma unroll
-        for (int q = 0; q < HC; ++q) I.MI[pp * TS + q] = w2[q];
-    if (L.row)
-#pragma unroll
-        for (int q = 0; q < HC; ++q) I.TI[pp * TS + q] = quxs[q];
-    SSYNC();
-    // G = Qx - Qux_c^T Quu_cc^-1 Qu_c = Qx + Qux_c^T dU_c (SinglePhase.cpp:359)
-    real gq4[4] = {qx, 0, 0, 0};
-#pragma unroll
-    for (int q = 0; q < HC; ++q) gq4[q & 3] = __builtin_fma(quxs[q], I.MI[NX * TS + q], gq4[q & 3]);
-    const real gq = (gq4[0] + gq4[1]) + (gq4[2] + gq4[3]);
-    if constexpr (DV) {
-        real dq = 0;
-#pragma unroll
-        for (int q = 0; q < HC; ++q) dq = __builtin_fma(quxs[q], I.MI[NX * TS + q], dq);
-        const double v = pp == NX ? (double)dq : zl ? (double)quz * (double)I.du[du_z] : 0.0;
-        if (st) dvs += v;
-    }
-    STAMP(7);
-    // ---- H = Qxx - Qux_c^T Quu_cc^-1 Qux_c = Qxx + Qux_c^T K_c on the matrix cores ------------------
-    // (tiles (0,0), (0,1), (1,1) of the symmetric 24 x 24 product, K = 12, for both items at once;
-    // rows / columns 24..31 only feed discarded outputs; SinglePhase.cpp:360)
-    const int li = L.lane & 15, lk = L.lane >> 4;
-    real a0[2][3], a1[2][3], b0[2][3], b1[2][3];
-#pragma unroll
-    for (int ei = 0; ei < 2; ++ei)
-#pragma unroll
-        for (int ks = 0; ks < 3; ++ks) {
-            const int q = 4 * ks + lk;
-            a0[ei][ks] = S.it[ei].TI[li * TS + q];
-            a1[ei][ks] = S.it[ei].TI[(16 + li) * TS + q];
-            b0[ei][ks] = S.it[ei].MI[li * TS + q];
-            b1[ei][ks] = S.it[ei].MI[(16 + li) * TS + q];
-        }
-    acc4<real> t00[2], t01[2], t11[2];
-#pragma unroll
-    for (int ei = 0; ei < 2; ++ei) t00[ei] = t01[ei] = t11[ei] = acc4<real>{0, 0, 0, 0};
-#pragma unroll
-    for (int ks = 0; ks < 3; ++ks)
-#pragma unroll
-        for (int ei = 0; ei < 2; ++ei) {
-            t00[ei] = mfma16(a0[ei][ks], b0[ei][ks], t00[ei]);
-            t01[ei] = mfma16(a0[ei][ks], b1[ei][ks], t01[ei]);
-            t11[ei] = mfma16(a1[ei][ks], b1[ei][ks], t11[ei]);
-        }
-    SSYNC();  // the operands are in registers: the product overwrites the K^T images
-#pragma unroll
-    for (int ei = 0; ei < 2; ++ei) {
-        real *P = S.it[ei].MI;
-#pragma unroll
-        for (int gi = 0; gi < 4; ++gi) {
-            const int r0 = mfma_row<real>(lk, gi), r1 = 16 + r0, c1 = 16 + li;
-            P[r0 * MS + li] = t00[ei][gi];
-            if (c1 < NX) {
-                P[r0 * MS + c1] = t01[ei][gi];
-                P[c1 * MS + r0] = t01[ei][gi];
-            }
-            if (r1 < NX && c1 < NX) P[r1 * MS + c1] = t11[ei][gi];
-        }
-    }
-    SSYNC();
-    STAMP(8);
-    const real *prow = L.row ? I.MI + pp * MS : S.zero;
-#pragma unroll
-    for (int c = 0; c < NX; ++c) h[c] = qxx[c] + prow[c];
-#else
     SSYNC();
     // K_c columns of both DPP rows at every DPP position (column c of the item on position c & 15
     // of ka (c < 16) or kb (c >= 16)); the coupled dU_c is position 24's: kb at position 8
@@ -638,247 +647,17 @@ DEV void knot(const Params &p, Lds<real> &S, const Lane &L, const Phase<real> &p
         const double v = pp == NX ? (double)dq : zl ? (double)quz * (double)(-(quz / qzz)) : 0.0;
         if (st) dvs += v;
     }
-    STAMP(7);
+    if constexpr (!CS) STAMP(7);
     // ---- H = Qxx - Qux_c^T Quu_cc^-1 Qux_c = Qxx + Qux_c^T K_c (SinglePhase.cpp:360): row pp,
     // K_c by DPP broadcast from the lanes that hold its columns
-#pragma unroll
-    for (int c = 0; c < NX; ++c) h[c] = qxx[c];
-    static_for<HC>([&](auto Q) {
+    if constexpr (CS) {
         static_for<NX>([&](auto C) {
-            constexpr int c = C;
-            if constexpr (c < 16)
-                bfma<c & 15>(h[c], ka[Q], quxs[Q]);
-            else
-                bfma<c & 15>(h[c], kb[Q], quxs[Q]);
+            if constexpr (cs_mine<W>(C)) h[C] = qxx[C];
         });
-    });
-    if constexpr (DV)
-        if (!L.row)
+    } else {  // (the whole row: kept a plain array copy, which the compiler treats as one)
 #pragma unroll
-            for (int c = 0; c < NX; ++c) h[c] = 0;
-    STAMP(8);
-#endif
-    g = L.row ? gq : (real)0;
-    // K_c rows and dU (SinglePhase.cpp:354-356).  Issued after a wait for all vector memory
-    // operations — the next knot's image DMA (requested before the elimination) and the previous
-    // knot's stores, both long complete — so no later wait counts these stores: the next knot reads
-    // its images without waiting (vector memory operations complete in order).
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if HSDDP_VALUE_MFMA
-    if (st && L.row) {
-        real *Kg = it.K + (size_t)kc * KCW;
-#pragma unroll
-        for (int q = 0; q < HC; ++q) Kg[q * NX + pp] = w2[q];
-        it.dU[(size_t)kc * NX + pp] = I.du[pp];
+        for (int c = 0; c < NX; ++c) h[c] = qxx[c];
     }
-#else
-    // from the row-pair copies (w2 is dead after the broadcast): columns 0..15 from ka by both DPP
-    // rows of the item (the two write the same value), columns 16..23 from kb
-    if (st) {
-        real *Kg = it.K + (size_t)kc * KCW;
-#pragma unroll
-        for (int q = 0; q < HC; ++q) Kg[q * NX + pos] = ka[q];
-        if (pos < NX - 16)
-#pragma unroll
-            for (int q = 0; q < HC; ++q) Kg[q * NX + 16 + pos] = kb[q];
-        if (L.row) it.dU[(size_t)kc * NX + pp] = I.du[pp];
-    }
-#endif
-    SSYNC();
-    STAMP(9);
-}
-
-// Workgroup barrier of the column split: this wave's LDS writes done, both waves here.  No wait
-// for vector memory (the knot images and the K / dU stores stay in flight: each wave waits for its
-// own requests with vmcnt before the barrier that publishes them).
-#define CSYNC()                                              \
-    do {                                                     \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-        __builtin_amdgcn_s_barrier();                        \
-        asm volatile("" ::: "memory");                       \
-        __builtin_amdgcn_sched_barrier(0);                   \
-    } while (0)
-
-// fetch for the column split: wave W requests its half of the two items' pieces into image buffer q
-template <int W, typename real>
-DEV void fetch_cs(LdsCS<real> &S, int q, const real *rec0, const real *def0, const real *rec1, const real *def1,
-                  int lane)
-{
-    using PC = Pieces<real>;
-    constexpr int H = (PC::NI + 1) / 2;
-#pragma unroll
-    for (int u = 0; u < H; ++u) {
-        const int t = W * H + u;
-        const int n = 64 * t + lane;
-        if (t < PC::NI && n < 2 * PC::NP) {
-            const int e = n >= PC::NP, qq = n - e * PC::NP;
-            const real *rec = e ? rec1 : rec0, *def = e ? def1 : def0;
-            const real *src = qq < PC::NA ? rec + PC::E * qq : qq < PC::NA + PC::ND ? def + PC::E * (qq - PC::NA)
-                                                                                    : rec + PC::E * (qq - PC::ND);
-            lds_dma16(src, (unsigned)(size_t)(&S.img[q][0][0]) + 1024u * t);
-        }
-    }
-}
-
-// One knot of the sweep for wave W of the column split (k_riccati_cs): the knot() stages with the
-// column-parallel work halved — T's controls 6 W .. 6 W + 5, the columns cs_wave(c) == W of M, Z,
-// Qxx and H — and the per-element chain (Gn, Qux_c, the Quu_cc columns, the elimination, the K
-// broadcast, G) formed whole in both waves, so each wave holds everything it multiplies by.  Three
-// barriers: M / T rows written -> column reads; Z rows written -> Qxx reads; this wave's H columns
-// written (and its share of the next images landed) -> the other wave's H columns read.  ib: the
-// image buffer of this knot (the next knot's go to ib ^ 1); par: which MZ image holds M (the
-// other takes Z).  Both waves run the same branch decisions (live, the PSD test) on equal values.
-template <int W, bool DV, typename real>
-DEV void knot_cs(const Params &p, LdsCS<real> &S, const Lane &L, const Phase<real> &ph, const Item<real> &it, int kc,
-                 real (&h)[NX], real &g, bool &live, bool first, bool more, int ib, int par, const real *nrec0,
-                 const real *ndef0, const real *nrec1, const real *ndef1, double &dvs)
-{
-    constexpr int Q0 = 6 * W, Q1 = Q0 + 6;
-    auto &I = S.it[L.e];
-    const real *img = S.img[ib][L.e];
-    real *const MA = I.MZ[par], *const ZA = I.MZ[par ^ 1];
-    const int pp = L.pp, pos = L.pos;
-    const real dt = (real)p.dt;
-    const real reg = it.reg;
-    if (first) {  // the phase's first images (each wave waits for its own requests, then both)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        CSYNC();
-    }
-    real cf[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) cf[k] = img[16 * k + pos];
-    real bv[4], bq[4];
-#pragma unroll
-    for (int l = 0; l < 4; ++l) { bv[l] = I.pc[l]; bq[l] = I.pc[4 + l]; }
-    // ---- Gn = G + H d, T = H B_c (this wave's controls), M = H A (this wave's columns) -------------
-    real t[HC], ga[4] = {g, 0, 0, 0};
-#pragma unroll
-    for (int q = 0; q < HC; ++q) t[q] = 0;
-    emit_Bc<Q0, Q1>(t, h[6], h[7], h[8], h + 9, h + 12, bv, bq, cf);
-    static_for<NX>([&](auto C) { vfma<V_D + C>(ga[C & 3], cf, h[C]); });
-    const real gn = (ga[0] + ga[1]) + (ga[2] + ga[3]);
-    pin(t);
-    real h9[NX];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) h9[j] = h[j];
-#pragma unroll
-    for (int j = 9; j < NX; ++j) h9[j] = 0;
-    SSYNC();
-    real (&m)[NX] = h;
-    emit_SA<W>(m, h9, cf, dt);
-    pin(t);
-    pin(m);
-    if (L.row) {
-        static_for<NX>([&](auto C) {
-            if constexpr (cs_mine<W>(C)) MA[pp * MS + C] = m[C];
-        });
-        if (W == 0) MA[pp * MS + NX] = gn;
-#pragma unroll
-        for (int q = Q0; q < Q1; ++q) I.TI[pp * TS + q] = t[q];
-    }
-    CSYNC();
-    // ---- column pp of M (position 24: Gn); Z row (this wave's columns), Qux_c column, Qu_c ----------
-    const int pc = pp < MS - 1 ? pp : MS - 1;
-    real mc[NX];
-#pragma unroll
-    for (int j = 0; j < NX; ++j) mc[j] = MA[j * MS + pc];
-    real w2[HC];
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {
-        const real *lcp = pp == NX ? img + V_LU + (((ph.cmask >> l) & 1) ? 3 * l : 12 + 3 * l) : S.zero;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) w2[3 * l + a] = lcp[a];
-    }
-    emit_SA<W>(m, mc, cf, dt);
-    emit_Bc(w2, mc[6], mc[7], mc[8], mc + 9, mc + 12, bv, bq, cf);
-    pin(m);
-    pin(w2);
-    // ---- Qxx = lxx + reg I + (Z + Z^T) / 2 on this wave's columns ----------------------------------
-    if (pp <= NX) {
-        static_for<NX>([&](auto C) {
-            if constexpr (cs_mine<W>(C)) ZA[pp * MS + C] = m[C];
-        });
-        if (W == 0) {
-            ZA[pp * MS + NX] = 0;
-            ZA[pp * MS + NX + 1] = 0;
-        }
-    }
-    SSYNC();
-    if (L.row) {  // lxx and reg I on the entries of this wave's columns (behind its own Z stores)
-        real *zr = ZA + pp * MS;
-        if (cs_wave(pp) == W) lds_add(zr + pp, ph.lxd + reg);
-#pragma unroll
-        for (int t2 = 0; t2 < 4; ++t2) {
-            const int xc = L.xkind == 1 ? L.xc0 + 3 * t2 : L.xc0;
-            if (((ph.xmask >> t2) & 1) && cs_wave(xc) == W) lds_add(zr + xc, -ph.xw);
-        }
-    }
-    CSYNC();
-    const real *zrow = L.row ? ZA + pp * MS : S.zero;
-    real qxx[NX], zc[NX];
-    static_for<NX>([&](auto C) {
-        if constexpr (cs_mine<W>(C)) {
-            qxx[C] = zrow[C];
-            zc[C] = ZA[C * MS + pc];
-        }
-    });
-    static_for<NX>([&](auto C) {
-        if constexpr (cs_mine<W>(C)) qxx[C] = __builtin_fma(zc[C], (real)0.5, qxx[C] * (real)0.5);
-    });
-    const real qx = img[V_LX + (L.row ? pp : 0)] + (gn + ZA[NX * MS + pc]);
-    // ---- Quu_cc column pos = luu + reg + B_c^T T[:, pos] -------------------------------------------
-    real tcol[18];
-#pragma unroll
-    for (int j = 0; j < 18; ++j) tcol[j] = I.TI[(6 + j) * TS + pos];
-    real lbr[3];
-    const int aq = pos % 3;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) lbr[a] = (L.qlane ? img + L.rb[a] : S.zero + a)[0] + (a == aq ? ph.dtr + reg : (real)0);
-    const int lq = pos / 3;
-    real w[HC];
-#pragma unroll
-    for (int q = 0; q < HC; ++q) w[q] = (L.qlane && lq == q / 3) ? lbr[q % 3] : (real)0;
-    emit_Bc(w, tcol[0], tcol[1], tcol[2], tcol + 3, tcol + 6, bv, bq, cf);
-    pin(w);
-    const bool zl = pp < HC;
-    const int du_z = ((ph.cmask >> ((zl ? pp : 0) / 3)) & 1) ? 12 + pp : pp;
-    const real quz = img[zl ? V_LU + du_z : V_LU];
-    const real qzz = ph.dtrz + reg;
-    // the next knot's images into the other buffer (read last in the previous knot, before its last
-    // barrier)
-    if (more) fetch_cs<W>(S, ib ^ 1, nrec0, ndef0, nrec1, ndef1, L.lane);
-    // ---- PSD test + elimination on [Quu_cc | Qux_c | Qu_c] (both waves) ------------------------------
-    real quxs[HC];
-#pragma unroll
-    for (int q = 0; q < HC; ++q) quxs[q] = (L.row || (DV && pp == NX)) ? w2[q] : (real)0;
-    pin(quxs);
-    unsigned long long bad = __builtin_amdgcn_ballot_w64(zl && !(qzz > (real)1e-9));
-    eliminate(w, w2, bad);
-    const bool okh = L.e ? (bad >> 32) == 0 : (bad & 0xffffffffull) == 0;
-    live = live && okh;
-    const bool st = live;
-    // ---- dU through LDS (both waves write the same values) -------------------------------------------
-    if (pp == NX)
-#pragma unroll
-        for (int q = 0; q < HC; ++q) I.du[(((ph.cmask >> (q / 3)) & 1) ? 0 : 12) + q] = w2[q];
-    if (zl) I.du[du_z] = -(quz / qzz);
-    SSYNC();
-    real ka[HC], kb[HC];
-#pragma unroll
-    for (int q = 0; q < HC; ++q) row_pair_last(w2[q], ka[q], kb[q]);
-    real gq4[4] = {qx, 0, 0, 0};
-    static_for<HC>([&](auto Q) { bfma<8>(gq4[Q & 3], kb[Q], quxs[Q]); });
-    const real gq = (gq4[0] + gq4[1]) + (gq4[2] + gq4[3]);
-    if constexpr (DV) {  // as knot(): Qu_c^T dU_c on position 24, the decoupled controls' on pp < 12
-        real dq = 0;
-        static_for<HC>([&](auto Q) { bfma<8>(dq, kb[Q], quxs[Q]); });
-        const double v = pp == NX ? (double)dq : zl ? (double)quz * (double)(-(quz / qzz)) : 0.0;
-        if (st) dvs += v;
-    }
-    // ---- H = Qxx + Qux_c^T K_c on this wave's columns ------------------------------------------------
-    static_for<NX>([&](auto C) {
-        if constexpr (cs_mine<W>(C)) h[C] = qxx[C];
-    });
     static_for<HC>([&](auto Q) {
         static_for<NX>([&](auto C) {
             constexpr int c = C;
@@ -895,33 +674,44 @@ DEV void knot_cs(const Params &p, LdsCS<real> &S, const Lane &L, const Phase<rea
             static_for<NX>([&](auto C) {
                 if constexpr (cs_mine<W>(C)) h[C] = 0;
             });
+    if constexpr (!CS) STAMP(8);
     g = L.row ? gq : (real)0;
-    // this wave's H columns into the M image (its column reads ended before the last barrier)
-    if (L.row)
-        static_for<NX>([&](auto C) {
-            if constexpr (cs_mine<W>(C)) MA[pp * MS + C] = h[C];
-        });
-    // K_c rows and dU: wave 0 columns 0..15, wave 1 columns 16..23 and dU; issued after this wave's
-    // image requests are complete (the barrier below publishes them)
+    // split: this wave's H columns into the M image (its column reads ended before the last barrier)
+    if constexpr (CS)
+        if (L.row)
+            static_for<NX>([&](auto C) {
+                if constexpr (cs_mine<W>(C)) MA()[pp * MS + C] = h[C];
+            });
+    // K_c rows and dU (SinglePhase.cpp:354-356).  Issued after a wait for all vector memory
+    // operations — the next knot's image DMA (requested before the elimination) and the previous
+    // knot's stores, both long complete — so no later wait counts these stores: the next knot reads
+    // its images without waiting (vector memory operations complete in order).
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // from the row-pair copies (w2 is dead after the broadcast): columns 0..15 from ka by both DPP
+    // rows of the item (the two write the same value), columns 16..23 from kb.  Split: wave 0 stores
+    // columns 0..15, wave 1 columns 16..23 and dU.
     if (st) {
         real *Kg = it.K + (size_t)kc * KCW;
-        if (W == 0) {
+        if constexpr (W <= 0) {
 #pragma unroll
             for (int q = 0; q < HC; ++q) Kg[q * NX + pos] = ka[q];
-        } else {
+        }
+        if constexpr (W != 0) {
             if (pos < NX - 16)
 #pragma unroll
                 for (int q = 0; q < HC; ++q) Kg[q * NX + 16 + pos] = kb[q];
             if (L.row) it.dU[(size_t)kc * NX + pp] = I.du[pp];
         }
     }
-    CSYNC();
-    // the other wave's columns of row pp
-    static_for<NX>([&](auto C) {
-        if constexpr (!cs_mine<W>(C)) h[C] = L.row ? MA[pp * MS + C] : (real)0;
-    });
+    if constexpr (CS) {
+        CSYNC();  // (publishes this wave's H columns and its share of the next images)
+        // the other wave's columns of row pp
+        static_for<NX>([&](auto C) {
+            if constexpr (!cs_mine<W>(C)) h[C] = L.row ? MA()[pp * MS + C] : (real)0;
+        });
+    }
     SSYNC();
+    if constexpr (!CS) STAMP(9);
 }
 
 // MultiPhaseDDP::backward_sweep (MultiPhaseDDP.cpp:190-229) for the wave's two items with their
@@ -1030,14 +820,11 @@ DEV int sweep_pair(const Params &p, const Bufs &d, LdsT &S, const Lane &L, const
             const bool more = k > 0;
             const int kn = more ? k - 1 : 0;
             const bool was = live;
+            knot<CSW, DV>(p, S, L, ph, it, k0 + k, h, g, live, k == N - 1, more, ib, par, recp(b0, kn), defp0(kn),
+                          recp(b1, kn), defp1(kn), dvs);
             if constexpr (CS) {
-                knot_cs<CSW, DV>(p, S, L, ph, it, k0 + k, h, g, live, k == N - 1, more, ib, par, recp(b0, kn),
-                                 defp0(kn), recp(b1, kn), defp1(kn), dvs);
                 ib ^= more ? 1 : 0;
                 par ^= 1;
-            } else {
-                knot<real, DV>(p, S, L, ph, it, k0 + k, h, g, live, k == N - 1, more, recp(b0, kn), defp0(kn), recp(b1, kn),
-                               defp1(kn), dvs);
             }
             if (was && !live) fail = k0 + k;
             if (!__builtin_amdgcn_ballot_w64(live)) break;
@@ -1138,6 +925,25 @@ DEV void zero_init(LdsT &S, int lane)
     SSYNC();
 }
 
+// The element of this half of pair `pair`: 2 pair + e, or the pair's entry of Bufs::pairs (elements
+// paired by layout).  An empty half (valid false) runs on the other half's element, inactive.
+// (Idx: the callers' index types, int and unsigned, kept as they are.)
+template <bool EL, typename Idx>
+DEV void pair_element(const Params &p, const Bufs &d, const Lane &L, Idx pair, int &bv, bool &valid)
+{
+    int b;
+    if constexpr (EL) {
+        const int e0 = d.pairs[2 * pair], e1 = d.pairs[2 * pair + 1];
+        b = L.e ? e1 : e0;
+        valid = b >= 0;
+        bv = valid ? b : (L.e ? e0 : e1);
+    } else {
+        b = 2 * pair + L.e;
+        valid = b < p.B;
+        bv = valid ? b : p.B - 1;
+    }
+}
+
 }  // namespace sweep
 
 using namespace sweep;
@@ -1160,21 +966,11 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB ==
 #if HSDDP_STAMPS
     if (L.lane < 12) S.st[L.lane] = 0;
 #endif
-    // the wave's two elements: 2 pair + e, or a pair of elements with one layout (Bufs::pairs);
-    // an empty half runs on the other half's element, inactive
-    int b, bv;
-    bool valid;
-    if constexpr (EL) {
+    if constexpr (EL)
         if (pair >= p.n_pairs) return;
-        const int e0 = d.pairs[2 * pair], e1 = d.pairs[2 * pair + 1];
-        b = L.e ? e1 : e0;
-        valid = b >= 0;
-        bv = valid ? b : (L.e ? e0 : e1);
-    } else {
-        b = 2 * pair + L.e;
-        valid = b < p.B;
-        bv = valid ? b : p.B - 1;
-    }
+    int bv;
+    bool valid;
+    pair_element<EL>(p, d, L, pair, bv, valid);
     ElemState &E = d.el[bv];
     bool act = valid && !E.done && !E.inner_done;
     if (!__builtin_amdgcn_ballot_w64(act)) return;
@@ -1243,29 +1039,21 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB ==
 }
 
 // k_riccati for small batches (column split, launch_riccati's choice): one element pair per
-// workgroup of two waves, wave W running sweep_pair with knot_cs<W> — the same sweeps, attempts and
+// workgroup of two waves, wave W running sweep_pair with knot<W> — the same sweeps, attempts and
 // outcomes as k_riccati (each wave computes the values the other multiplies by, so both take the
 // same branches); wave 0 alone writes the element state and the retry list.  fp64; DV: single
-// shooting's dV from the sweep, as k_riccati.  At small batches k_riccati runs one wave per SIMD and its knot is one dependent chain
-// of ~11 k cycles; split, each wave issues ~970 of the 1 197 VALU instructions of a knot (static
-// count of the knot loops) and the knot takes ~10 % less (sweep_split).
+// shooting's dV from the sweep, as k_riccati.  At small batches k_riccati runs one wave per SIMD
+// and its knot is one dependent chain of ~11 k cycles; split, each wave issues ~970 of the 1 197
+// VALU instructions of a knot (static count of the knot loops) and the knot takes ~10 % less
+// (sweep_split).
 template <bool EL, bool DV, int W>
 DEV void riccati_cs_wave(const Params &p, const Bufs &d, LdsCS<double> &S)
 {
     using real = double;
     const Lane L = make_lane();
-    int b, bv;
+    int bv;
     bool valid;
-    if constexpr (EL) {
-        const int e0 = d.pairs[2 * blockIdx.x], e1 = d.pairs[2 * blockIdx.x + 1];
-        b = L.e ? e1 : e0;
-        valid = b >= 0;
-        bv = valid ? b : (L.e ? e0 : e1);
-    } else {
-        b = 2 * blockIdx.x + L.e;
-        valid = b < p.B;
-        bv = valid ? b : p.B - 1;
-    }
+    pair_element<EL>(p, d, L, blockIdx.x, bv, valid);
     ElemState &E = d.el[bv];
     bool act = valid && !E.done && !E.inner_done;
     // (act is the same in both waves: both return here, or neither)

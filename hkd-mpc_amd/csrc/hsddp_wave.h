@@ -161,17 +161,6 @@ DEV void vfma(T &acc, const T (&cf)[NC], T x)
     bfma<(n & 15)>(acc, cf[n >> 4], x);
 }
 
-// D = A B + C on a 16 x 16 x 4 MFMA tile (one operand value per lane: A[l & 15][l >> 4],
-// B[l >> 4][l & 15]); result register g of lane l is row mfma_row(l >> 4, g), column l & 15 — the
-// f64 form interleaves rows, the f32 form blocks them (cdna_hip_programming.md, fragment layout)
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-DEV d4 mfma16(double a, double b, d4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-DEV f4 mfma16(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-template <typename real> using acc4 = std::conditional_t<sizeof(real) == 8, d4, f4>;
-template <typename real>
-DEV constexpr int mfma_row(int lk, int g) { return sizeof(real) == 8 ? lk + 4 * g : 4 * lk + g; }
-
 // One LDS-DMA instruction: 16 bytes per active lane from `src` to LDS at m0 + 16 * lane (inline
 // asm: the compiler neither waits for it nor knows it writes LDS — the consumer waits with
 // vmcnt).  M0 is compiler-reserved: saved, set with one wait state before the DMA, restored.
