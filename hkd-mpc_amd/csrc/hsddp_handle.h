@@ -1,0 +1,202 @@
+// hsddp_handle.h — the handle behind include/hsddp.h and the host helpers its source files share
+// (private to csrc): hsddp_api.cpp (handle, layouts, transfers), hsddp_solve.cpp (the solve loop),
+// hsddp_horizon.cpp (the MPC caller's side: commands, shift, references, hsddp_advance) and
+// hsddp_settings.cpp (defaults and the INFO loaders).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/hsddp.h"
+#include "hsddp_internal.h"
+
+namespace hsddp {
+// records the calling thread's hsddp_last_error text; returns code (hsddp_api.cpp)
+int fail(int code, const std::string &msg);
+}  // namespace hsddp
+
+#define HIPCHK(expr)                                                                                 \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess) return hsddp::fail(HSDDP_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+struct hsddp_handle_t {
+    using Params = hsddp::Params;
+    using Bufs = hsddp::Bufs;
+    using Layout = hsddp::Layout;
+    // the slot costs / |Defect|^2 of the last rollout (k_rollout's per-slot outputs) belong to the
+    // working trajectory under the current cost parameters: k_lq need not recompute them
+    bool slots_fresh = false;
+    // every per-knot ReB (delta, eps) still equals the descriptor's initial pair, so the kernels may
+    // read the two scalars (Params::reb_uniform) when the schedule keeps them there
+    bool reb_at_init = true;
+    hsddp_problem_desc desc;
+    hsddp_options opt;
+    Params p;
+    Bufs d;
+    hipStream_t stream = nullptr;
+    int *host_counter = nullptr;                // [16]: k_count's activity counts, stat sums, the graphs' counts
+    std::vector<hipEvent_t> events;             // the stats timer's pool (reused, destroyed with the handle)
+    // hsddp_solve's inner iteration + activity count as replayed hipGraphs (early-exit mode), keyed
+    // by the launch arguments they froze; a small cache so the receding-horizon tick's recurring
+    // layouts and swapped warm-start buffers find theirs again (round-robin eviction)
+    struct IterGraph {
+        hipGraphExec_t exec = nullptr;
+        Params p;
+        Bufs d;
+        double alpha = 0;
+        int par = 0;  // which host count slot (host_counter[8 + 4 * par + 1]) its copy fills
+    } iter_graph[8];
+    int iter_graph_next = 0;
+    // hsddp_advance's shift without its own synchronisation: the host rows its pageable copies read
+    // stay here until the advance synchronises, and the touchdown-overflow flag is read then
+    std::vector<std::vector<int>> shift_keep;
+    bool shift_overflow_pending = false;
+    size_t scratch_reserved = 0;  // scratch bytes the pending shift's maps occupy (build_refs goes after)
+    hipEvent_t iter_done[2] = {nullptr, nullptr};  // recorded after each replay, by parity
+    std::vector<void *> allocs;
+    size_t bytes = 0;
+    int Bref = 1;
+    bool have_problem = false;
+    std::vector<int> contacts;  // host copy [B][P+1][4]: maps the compact K rows to controls
+    bool contacts_current = false;  // `contacts` belong to the current layout (not stale after a shift)
+    void *scratch = nullptr;    // device staging for the MPC-side calls (grown on demand)
+    size_t scratch_bytes = 0;
+    // receding-horizon state (HKDProblemData, HKDProblem.h:20-66): is_phase_reach_end per phase,
+    // state-slot capacity (a shift keeps Kc and may add phases), and the second set of compact gain
+    // rows the shift gathers into (allocated by the first shift; the new Xbar / Ubar rows go to each
+    // element's third trajectory buffer)
+    std::vector<int> reach_end;
+    size_t S_cap = 0;
+    void *spare_K = nullptr;
+    // ... and of the constraint parameters the phases carry (ReB per knot, touchdown constraints)
+    double *spare_reb_delta = nullptr, *spare_reb_eps = nullptr, *spare_al_sigma = nullptr, *spare_al_lambda = nullptr;
+    int *spare_td_mask = nullptr;
+    double *spare_cf_u = nullptr;
+    int *spare_cf_flag = nullptr;
+    double *shift_stage = nullptr;  // [3][B][S_cap][24] (ShiftArgs::stage), at the first stride-changing shift
+    bool need_inputs = false;   // a shift changed the layout: update_problem before solving
+    double *ref_table = nullptr;  // reference samples [n][RT_W] (hsddp_set_reference_table)
+    int ref_n = 0;
+    float ref_dt = 0;
+    bool refs_on_device = false;  // references built by hsddp_build_references for this layout
+    bool ref_cols_stale = true;   // Bufs::ref_t behind the reference rows (refreshed by begin_launches)
+    // reference-driven MPC state (hsddp_advance): the table's samples on the host (contacts and
+    // durations are read there), each reference element's window start, the window length and
+    // the simulation step of the last hsddp_build_references, QuadReference::t_cur, and the
+    // contact durations of every element's phases [B][P][4] (HKDProblemData::contact_durations)
+    std::vector<hsddp_quad_state> table_host;
+    std::vector<int> win_start;
+    int win_len = 0;
+    float dt_sim = 0, t_cur = 0;
+    std::vector<double> durations;
+    int retry_cap_alloc = 0, retry_m_alloc = 0;  // parallel regularisation retry scratch (k_riccati_retry)
+    float *hist = nullptr;  // solver-info history [B][p.hcap][4] (grown by ensure_history)
+    // per-element layouts (hsddp_set_element_layouts): host copies of Bufs::lay; empty = the handle's
+    // shared one (adopt_shared_layout; Params carries its N / s0 / k0 / ss to the kernels)
+    Layout shared{};
+    std::vector<Layout> lays;
+    std::vector<int> reach_el;  // [B][16] is_phase_reach_end per element (with per-element layouts)
+    double *value0 = nullptr;  // G[0], H[0] per phase [B][16][600] (hsddp_set_value_export)
+    // asynchronous command extraction (hsddp_extract_commands_async): two device record buffers, two
+    // pinned host buffers, a copy stream and per buffer the event of its last copy
+    hsddp_mpc_command *cmd_dev[2] = {nullptr, nullptr}, *cmd_host[2] = {nullptr, nullptr};
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t cmd_ready[2] = {nullptr, nullptr}, cmd_copied[2] = {nullptr, nullptr};
+    char *cmd_in_host[2] = {nullptr, nullptr};  // pinned staging of each ticket's durations / feet
+    size_t cmd_in_bytes[2] = {0, 0};
+    int cmd_next = 0;
+};
+
+namespace hsddp {
+
+// device staging area of at least `bytes` (contents not preserved when it grows)
+inline int scratch(hsddp_handle h, size_t bytes, char **out)
+{
+    if (bytes > h->scratch_bytes) {
+        if (h->scratch) hipFree(h->scratch);
+        h->scratch = nullptr;
+        h->scratch_bytes = 0;
+        hipError_t e = hipMalloc(&h->scratch, bytes);
+        if (e != hipSuccess) return fail(HSDDP_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
+        h->scratch_bytes = bytes;
+    }
+    *out = (char *)h->scratch;
+    return HSDDP_OK;
+}
+
+// the layout of element b: the handle's, or its own (hsddp_set_element_layouts)
+inline const Layout &layout_of(hsddp_handle h, size_t b)
+{
+    return h->lays.empty() ? h->shared : h->lays[b];
+}
+
+// is_phase_reach_end of element b's phases
+inline const int *reach_of(hsddp_handle h, size_t b)
+{
+    return h->lays.empty() ? h->reach_end.data() : &h->reach_el[b * HSDDP_MAX_PHASES];
+}
+
+// phase of control slot kc in a layout
+inline int phase_of_control(const Layout &L, int kc)
+{
+    int i = 0;
+    while (i + 1 < L.P && kc >= L.k0[i + 1]) ++i;
+    return i;
+}
+
+// control u of compact gain row q at control slot k of element b (KCW layout, hsddp_internal.h)
+inline int coupled_control(hsddp_handle h, size_t b, size_t k, int q)
+{
+    const Params &p = h->p;
+    const int i = phase_of_control(layout_of(h, b), (int)k);
+    const int c = h->contacts[(b * (p.P + 1) + i) * 4 + q / 3];
+    return c ? q : 12 + q;
+}
+
+template <typename T>
+inline int dalloc(hsddp_handle h, T *&ptr, size_t n)
+{
+    void *p = nullptr;
+    size_t sz = n * sizeof(T);
+    if (sz == 0) sz = 16;
+    hipError_t e = hipMalloc(&p, sz);
+    if (e != hipSuccess) return fail(HSDDP_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
+    // zeroed on the handle's stream once it exists: the null stream is not ordered with a
+    // non-blocking stream, so a null-stream memset of a buffer allocated mid-solve (the shift's
+    // spares) could land after the kernel that fills it
+    if (h->stream) hipMemsetAsync(p, 0, sz, h->stream);
+    else {
+        hipMemset(p, 0, sz);
+        hipStreamSynchronize(nullptr);
+    }
+    h->allocs.push_back(p);
+    h->bytes += sz;
+    ptr = (T *)p;
+    return HSDDP_OK;
+}
+
+inline int h2d(void *dst, const void *src, size_t bytes, hipStream_t st)
+{
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
+    return HSDDP_OK;
+}
+
+inline int d2h(void *dst, const void *src, size_t bytes)
+{
+    if (!dst) return HSDDP_OK;
+    HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return HSDDP_OK;
+}
+
+// hsddp_api.cpp
+// install per-element layouts: device records, sweep pairs (equal layouts share a wave), strides
+int set_layouts(hsddp_handle h, const std::vector<Layout> &lays);
+// the handle takes the shared layout L with the phases' reach flags (null: none reached): Params,
+// the descriptor's n_phases / horizons; per-element layouts and their flags are dropped
+void adopt_shared_layout(hsddp_handle h, const Layout &L, const int *reach);
+
+}  // namespace hsddp

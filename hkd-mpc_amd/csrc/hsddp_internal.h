@@ -21,12 +21,12 @@
 
 #include <hip/hip_runtime.h>
 #include "hkd_model.h"
+#include "hsddp_phases.h"
 
 namespace hsddp {
 
 constexpr int NX = 24;
 constexpr int NN = 576;
-constexpr int MAXP = 16;
 constexpr int LS_LIVE = 128;  // line-search trials with a liveness flag (later ones run unconditionally)
 // TouchDownConstraint objects per phase (HSDDP_MAX_TD): HKDProblem::initialization registers one
 // per phase and HKDProblem::update one more at every step the last phase has reached its end
@@ -71,13 +71,7 @@ constexpr int TM_PX = TM_PHIXX + NN;
 constexpr int TW = TM_PX + NN;           // 1184
 static_assert(TM_PHIXX % 16 == 0 && TM_PX % 16 == 0 && TW % 16 == 0, "terminal record lines");
 
-// Phase layout of one element: P phases of N_i knots, state slots s0_i .. s0_i + N_i, control slots
-// k0_i .. k0_i + N_i - 1, shooting states ss_i; S = sum(N_i + 1).  Per-element layouts
-// (hsddp_set_element_layouts) all have the handle's Kc.
-struct Layout {
-    int P, S, has_tail, pad;
-    int N[MAXP], s0[MAXP], k0[MAXP], ss[MAXP];
-};
+// (struct Layout, the phase layout of one element, and MAXP: hsddp_phases.h)
 
 struct Params {
     // B elements; P, S: the handle's layout (with per-element layouts: the largest P and S, the
@@ -158,7 +152,7 @@ struct Bufs {
     // the same references entry-major, for kernels with one slot per lane (a lane's entry j is next to
     // its neighbours': one contiguous piece per wave instead of 64 rows): [REF_COLS][ref_tw], column
     // r = (ref_per_element ? b : 0) S + s, entries ref_x 0 .. 23, ref_u 24 .. 47, ref_foot 48 .. 59.
-    // Refreshed from the rows by launch_ref_columns whenever the rows change (hsddp_api.cpp)
+    // Refreshed from the rows by launch_ref_columns whenever the rows change (sync_ref_columns, hsddp_solve.cpp)
     double *ref_t;
     size_t ref_tw;
     // Trajectory::update_nominal_vals without copies: each element's nominal (Xbar, Ubar) and working

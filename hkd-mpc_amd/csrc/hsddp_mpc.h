@@ -19,7 +19,7 @@ struct CmdArgs {
     float solve_time;
 };
 
-// receding-horizon gather: new slot <- old slot (labels as hsddp_api.cpp ShiftPhase)
+// receding-horizon gather: new slot <- old slot (labels as ShiftPhase, hsddp_phases.h)
 struct ShiftArgs {
     int S_old, S_new, Kc;
     const int *smap, *cmap;   // [n_maps][S_new], [n_maps][Kc] device

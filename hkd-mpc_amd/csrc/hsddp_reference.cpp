@@ -10,8 +10,11 @@
 #include <string>
 
 #include "../../include/hsddp.h"
+#include "hsddp_phases.h"
 
 extern "C" int hsddp_ref_fail(int code, const char *msg);  // hsddp_api.cpp: sets hsddp_last_error
+
+using hsddp::sample_at;  // (QuadReference's sample rounding)
 
 namespace {
 
@@ -71,15 +74,6 @@ void reorder(hsddp_quad_state &q)
 bool approx_eq(float a, float b) { return std::abs(a - b) <= 1e-6f; }
 bool approx_leq(float a, float b) { return a < b || approx_eq(a, b); }
 bool approx_geq(float a, float b) { return a > b || approx_eq(a, b); }
-
-// sample index of relative time t (QuadReference.cpp:64-75, 81-91): left-clipped, moved right when
-// past the half step, clamped to the window end
-int sample_at(float t, float dt, int sz)
-{
-    int k = (int)std::floor(t / dt);
-    if (t - k * dt > 0.5 * dt) k++;
-    return k > sz ? sz : k;
-}
 
 }  // namespace
 
