@@ -490,7 +490,8 @@ static int reset_working(hsddp_handle h, bool params)
     if (params) launch_reset_working(p, d, h->stream);  // X = Xbar, U = Ubar (one buffer), Defect = 0
     // dX, du, dU: a new problem's are zero.  Between solves the initial rollout (eps = 0) does not
     // read them (fma_step / add_step) and the sweep and linear rollout rewrite them before any
-    // trial, so an update keeps them (474 MB of memsets at B = 4096 saved per MPC tick) — except dX
+    // trial, so an update keeps them (474 MB of memsets at B = 4096 saved per MPC tick; the shift
+    // moves their rows with the knots, DESIGN.md "MPC tick") — except dX
     // with single shooting, which no linear rollout writes: the trials read it (zero, as in a
     // problem that never ran multiple shooting; the reference's is never written there either)
     if (params || p.ms0) HIPCHK(hipMemsetAsync(d.dX, 0, B * S * NX * sizeof(double), h->stream));
@@ -574,9 +575,14 @@ extern "C" int hsddp_upload_constraint_params(hsddp_handle h, const double *reb_
     HIPCHK(hipSetDevice(h->desc.device));
     const Bufs &d = h->d;
     int rc;
+    if (td_legs) {  // merged on the device: TD_STALE and TD_PENDING are its own (k_upload_td)
+        char *buf;
+        if ((rc = scratch(h, nt * sizeof(int), &buf)) || (rc = h2d(buf, td_legs, nt * sizeof(int), h->stream))) return rc;
+        launch_upload_td(p, d, (const int *)buf, h->stream);
+        HIPCHK(hipGetLastError());
+    }
     if ((reb_delta && (rc = h2d(d.reb_delta, reb_delta, nr * sizeof(double), h->stream))) ||
         (reb_eps && (rc = h2d(d.reb_eps, reb_eps, nr * sizeof(double), h->stream))) ||
-        (td_legs && (rc = h2d(d.td_mask, td_legs, nt * sizeof(int), h->stream))) ||
         (al_sigma && (rc = h2d(d.al_sigma, al_sigma, nt * 4 * sizeof(double), h->stream))) ||
         (al_lambda && (rc = h2d(d.al_lambda, al_lambda, nt * 4 * sizeof(double), h->stream))))
         return rc;

@@ -78,6 +78,8 @@ struct hsddp_handle_t {
     double *spare_cf_u = nullptr;
     int *spare_cf_flag = nullptr;
     double *shift_stage = nullptr;  // [3][B][S_cap][24] (ShiftArgs::stage), at the first stride-changing shift
+    // ... and of the search direction (dX [B][S_cap][24]; dU, du [B][Kc][24]), which has one buffer each
+    double *spare_dX = nullptr, *spare_dU = nullptr, *spare_du = nullptr;
     bool need_inputs = false;   // a shift changed the layout: update_problem before solving
     double *ref_table = nullptr;  // reference samples [n][RT_W] (hsddp_set_reference_table)
     int ref_n = 0;

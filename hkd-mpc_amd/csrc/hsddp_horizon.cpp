@@ -233,6 +233,11 @@ static int shift_apply(hsddp_handle h, const ShiftPlan &plan, bool defer, int *o
             (rc = dalloc(h, h->spare_cf_u, B * p.Kc * 12)) || (rc = dalloc(h, h->spare_cf_flag, B * p.Kc)))
             return rc;
     }
+    if (!h->spare_dX) {
+        if ((rc = dalloc(h, h->spare_dX, B * h->S_cap * NX)) || (rc = dalloc(h, h->spare_dU, B * p.Kc * NX)) ||
+            (rc = dalloc(h, h->spare_du, B * p.Kc * NX)))
+            return rc;
+    }
     char *buf;
     const size_t nmaps = smap.size() + cmap.size() + rmap.size() + pmap.size() + nadd.size();
     if ((rc = scratch(h, (nmaps + (nk > 1 ? B : 0)) * sizeof(int), &buf))) return rc;
@@ -270,7 +275,8 @@ static int shift_apply(hsddp_handle h, const ShiftPlan &plan, bool defer, int *o
         if (!h->shift_stage && (rc = dalloc(h, h->shift_stage, 3 * B * h->S_cap * NX))) return rc;
         a.stage = h->shift_stage;
     }
-    launch_shift_gather(p.B, a, d, h->spare_K, h->stream);  // (working rows and sel too)
+    a.dX_new = h->spare_dX; a.dU_new = h->spare_dU; a.du_new = h->spare_du;
+    launch_shift_gather(p.B, a, d, h->spare_K, h->stream);  // (working rows, search direction and sel too)
     HIPCHK(hipGetLastError());
     // defer (hsddp_advance, one layout for the batch): the caller's host work runs under the gather;
     // everything after it is ordered on the handle's stream
@@ -283,6 +289,9 @@ static int shift_apply(hsddp_handle h, const ShiftPlan &plan, bool defer, int *o
     std::swap(d.td_mask, h->spare_td_mask);
     std::swap(d.cf_u, h->spare_cf_u);
     std::swap(d.cf_flag, h->spare_cf_flag);
+    std::swap(d.dX, h->spare_dX);
+    std::swap(d.dU, h->spare_dU);
+    std::swap(d.du, h->spare_du);
     const bool td_overflow = !async && h->host_counter[6] != 0;
     if (p.fp32) { float *t = d.K32; d.K32 = (float *)h->spare_K; h->spare_K = t; }
     else { double *t = d.K; d.K = (double *)h->spare_K; h->spare_K = t; }

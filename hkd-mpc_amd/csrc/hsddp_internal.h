@@ -217,6 +217,9 @@ void launch_reset_elements(const Params &p, const Bufs &d, hipStream_t st);
 void launch_init_params(const Params &p, const Bufs &d, hipStream_t st);
 // TD_PENDING touchdown masks resolved from the contact rows (after new contacts are uploaded)
 void launch_resolve_td(const Params &p, const Bufs &d, hipStream_t st);
+// the caller's leg masks legs [B][P][MTD] (device) merged into td_mask: unchanged slots keep their
+// TD_STALE / TD_PENDING bits, changed ones become new constraints (TD_STALE, ElemState::td_stale)
+void launch_upload_td(const Params &p, const Bufs &d, const int *legs, hipStream_t st);
 // Bufs::ref_t from the reference rows (Bref x S columns)
 constexpr int REF_COLS = 24 + 24 + 12;  // (ref_x, ref_u, ref_foot widths)
 void launch_ref_columns(const Params &p, const Bufs &d, int Bref, hipStream_t st);

@@ -1474,6 +1474,20 @@ __global__ __launch_bounds__(256) void k_resolve_td(Params p, Bufs d)
     m = legs ? legs | (m & TD_STALE) : 0;
 }
 
+// The caller's touchdown leg masks [B][P][MTD] (hsddp_upload_constraint_params) merged into the
+// device's: a slot whose legs are unchanged is the same constraint object and keeps its TD_STALE /
+// TD_PENDING bits (the caller never sees them); a slot that goes to 0 is cleared; any other is a new
+// constraint object, whose residual reads 0 until a rollout computes it.
+__global__ __launch_bounds__(256) void k_upload_td(Params p, Bufs d, const int *legs)
+{
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long)p.B * p.P * MTD) return;
+    const int old = d.td_mask[gid], nl = legs[gid] & 15;
+    if ((old & 15) == nl) return;
+    d.td_mask[gid] = nl ? nl | TD_STALE : 0;
+    if (nl) d.el[gid / ((long)p.P * MTD)].td_stale = 1;
+}
+
 // Bufs::ref_t: one thread per (entry j, column r), j-major so that the column stores are contiguous
 __global__ __launch_bounds__(256) void k_ref_columns(Bufs d, long ncol)
 {
@@ -1884,6 +1898,10 @@ void launch_init_params(const Params &p, const Bufs &d, hipStream_t st)
 void launch_resolve_td(const Params &p, const Bufs &d, hipStream_t st)
 {
     LAUNCH_EL(k_resolve_td, dim3(blocks_for((long)p.B * p.P * MTD, 256)), dim3(256), st, p, d);
+}
+void launch_upload_td(const Params &p, const Bufs &d, const int *legs, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_upload_td, dim3(blocks_for((long)p.B * p.P * MTD, 256)), dim3(256), 0, st, p, d, legs);
 }
 void launch_stat_sums(const Params &p, const Bufs &d, hipStream_t st)
 {

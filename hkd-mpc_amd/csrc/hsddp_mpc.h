@@ -31,10 +31,14 @@ struct ShiftArgs {
     // of its neighbours in a buffer another element still reads (every element picks its own
     // buffers); null: the strides agree and every element's rows stay inside its own region
     double *stage;
+    // second set of the single-buffered search direction (dX [B][S_cap][24]; dU, du [B][Kc][24]):
+    // its shifted rows are gathered here at the new stride and the caller swaps the sets afterwards
+    double *dX_new, *dU_new, *du_new;
 };
 // the new Xbar / Ubar rows into every element's third buffer, which becomes its nominal one; the
 // working rows (X, U, Defect) follow into the same buffer when they are the nominal ones, else into
-// the old nominal buffer (read by then), which becomes the working one; the new compact K rows into K_new
+// the old nominal buffer (read by then), which becomes the working one; the new compact K rows into
+// K_new; the search direction's rows (dX, dU, du) into a.dX_new, a.dU_new, a.du_new
 void launch_shift_gather(int B, const ShiftArgs &a, const Bufs &d, void *K_new, hipStream_t st);
 // constraint objects through the shift: ReB rows by control-slot source (rmap: old slot, -1 =
 // initial), the stored GRF values' table by control-slot source (cmap: old slot, -1 = a new knot,

@@ -11,7 +11,8 @@
 //                        warm start (Xbar, Ubar, K) re-laid for the shifted phases — dropped
 //                        front knots / phases, pushed-back copies of X.back(), zero new phases —
 //                        as one gather over (element, new slot, entry) from host-built slot maps;
-//                        k_shift_gather_work then the working rows (X, U, Defect) alike.
+//                        k_shift_gather_work then the working rows (X, U, Defect) alike, and
+//                        k_shift_gather_steps the search direction (dX, dU, du).
 #include <cstddef>
 #include "../../include/hsddp.h"
 #include "hsddp_device.h"
@@ -209,6 +210,36 @@ __global__ __launch_bounds__(256) void k_shift_gather_work(int B, ShiftArgs a, B
     *(double2 *)&ubuf(d, dst)[(b * nu + e) * 2] = v;
 }
 
+// The search direction through the same update: Trajectory::pop_front / push_back_state move dX
+// and dU with their knots (TrajectoryManagement.cpp:137,141,168,172,199,203; a pushed-back knot's
+// and a new phase's rows are zero), and du (= dU + K dX, the linear rollout's control step) is kept
+// beside dU.  dX rows by the state map, dU and du rows by the control map.  They have one buffer
+// each, so the new rows go to a second set (ShiftArgs::dX_new ..) that the host then swaps in: an
+// element reads its old rows at the old stride and writes at the new one, and no row of another
+// element is ever read.
+__global__ __launch_bounds__(256) void k_shift_gather_steps(int B, ShiftArgs a, Bufs d)
+{
+    const long nx = (long)a.S_new * NX / 2, nu = (long)a.Kc * NX / 2, per = nx + 2 * nu;
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long)B * per) return;
+    const long b = gid / per;
+    long e = gid % per;
+    const int m = a.map_id ? a.map_id[b] : 0;
+    double2 v = {0.0, 0.0};
+    if (e < nx) {
+        const int s = (int)(2 * e / NX), j = (int)(2 * e % NX), lab = a.smap[(size_t)m * a.S_new + s];
+        if (lab >= 0) v = *(const double2 *)&d.dX[(b * a.S_old + lab) * NX + j];
+        *(double2 *)&a.dX_new[(b * nx + e) * 2] = v;
+        return;
+    }
+    e -= nx;
+    const bool step = e >= nu;  // du after dU
+    if (step) e -= nu;
+    const int k = (int)(2 * e / NX), j = (int)(2 * e % NX), lab = a.cmap[(size_t)m * a.Kc + k];
+    if (lab >= 0) v = *(const double2 *)&(step ? d.du : d.dU)[(b * a.Kc + lab) * NX + j];
+    *(double2 *)&(step ? a.du_new : a.dU_new)[(b * nu + e) * 2] = v;
+}
+
 // new selection: nominal = the third buffer; working = the same, or the old nominal buffer
 __global__ void k_shift_sel(int B, Bufs d)
 {
@@ -234,6 +265,8 @@ void launch_shift_gather(int B, const ShiftArgs &a, const Bufs &d, void *K_new, 
         hipLaunchKernelGGL(k_shift_gather<double>, g, dim3(256), 0, st, B, a, d, d.K, (double *)K_new);
     const long nw = (long)B * ((long)a.S_new * NX + (long)a.Kc * NX / 2);
     hipLaunchKernelGGL(k_shift_gather_work, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, B, a, d);
+    const long ns = (long)B * ((long)a.S_new * NX / 2 + (long)a.Kc * NX);
+    hipLaunchKernelGGL(k_shift_gather_steps, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, B, a, d);
     hipLaunchKernelGGL(k_shift_sel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B, d);
 }
 

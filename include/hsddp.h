@@ -204,7 +204,13 @@ int hsddp_upload_warm_start(hsddp_handle h, const double *Xbar, const double *Ub
  * td_legs [B][P][HSDDP_MAX_TD]: the touchdown constraints of each phase in registration order,
  * bit l = leg l (0: no constraint in that slot); al_sigma, al_lambda [B][P][HSDDP_MAX_TD][4] per
  * constraint and leg (entries of legs outside the mask are ignored).  Any pointer may be NULL
- * (kept / not read).  Upload after the problem's contacts (hsddp_upload_problem). */
+ * (kept / not read).  Upload after the problem's contacts (hsddp_upload_problem).
+ * td_legs names constraint objects, not their stored values: a slot uploaded with the legs it
+ * already has stays the same object (its stored residual — zero until a rollout has computed it —
+ * is kept, and so is a constraint hsddp_shift appended whose legs the next contact rows decide,
+ * which downloads as 0); a slot whose legs change, or that goes from 0 to a mask, is a new
+ * constraint whose residual reads 0 until a rollout reaches its phase end; a slot set to 0 is
+ * removed.  A download followed by an upload of the same arrays therefore changes nothing. */
 int hsddp_upload_constraint_params(hsddp_handle h, const double *reb_delta, const double *reb_eps, const int *td_legs,
                                    const double *al_sigma, const double *al_lambda);
 int hsddp_download_constraint_params(hsddp_handle h, double *reb_delta, double *reb_eps, int *td_legs,
@@ -355,8 +361,11 @@ int hsddp_set_layout(hsddp_handle h, int n_phases, const int *horizons, const in
  * registers: their legs are the new contact rows' touchdown legs).  The working trajectory (X, U,
  * Defect) and the constraint objects' stored values carry over too (shifted alike): a solve whose
  * initial rollout diverges keeps them past its break, as the reference's objects do.  Resets the
- * per-element solver state (dX, dU and du keep their values: the next solve rewrites them before
- * any line-search trial reads them; with MS false dX is reset to 0). */
+ * per-element solver state.  The search direction (dX, dU, du) keeps its values — the next solve
+ * rewrites them before any line-search trial reads them; with MS false dX is reset to 0 — and
+ * hsddp_shift, hsddp_shift_elements and hsddp_advance move its rows with their knots, element by
+ * element, as Trajectory::pop_front / push_back_state do (a pushed-back knot's and a new phase's
+ * rows are zero): hsddp_download_working after a shift returns the shifted dX and dU. */
 int hsddp_update_problem(hsddp_handle h, const int *contacts, const double *x0, const double *ref_x,
                          const double *ref_u, const double *ref_foot);
 

@@ -123,21 +123,30 @@ def shift(horizons, shooting, reach_end, Xbar, X, Ubar, K, contact_change):
     return hz, ss, re, flat(xb), flat(ub), flat(kk)
 
 
-def shift_working(horizons, reach_end, X, U, Defect, contact_change):
+def shift_working(horizons, reach_end, X, U, Defect, contact_change, dX=None, dU=None):
     """The same update on one element's working trajectory, which the reference keeps from tick to
     tick beside the nominal one (a solve whose last line search failed leaves X, U != Xbar, Ubar,
     quirk A2; a later initial rollout that breaks keeps them past the break): Trajectory::pop_front
     drops the front rows of X, U and Defect (TrajectoryManagement.cpp:118-145), push_back_state
     appends X.back() to X, a zero U row and a zero Defect row (:179-207), a new phase starts from
-    zeros (Trajectory::create_data).  Returns (X, U, Defect) in the flat slot layout."""
+    zeros (Trajectory::create_data).  Returns (X, U, Defect) in the flat slot layout.  With dX
+    ([S][24]) and dU ([Kc][24]) the search direction follows as the reference's does — pop_front
+    drops their front rows (:137,141), push_back_state appends zero rows (:199,203), a new phase's
+    are zero — and the result is (X, U, Defect, dX, dU)."""
     hz, re = list(horizons), list(reach_end)
     xw, dw, uw = split_phases(X, hz, True), split_phases(Defect, hz, True), split_phases(U, hz, False)
+    steps = dX is not None or dU is not None
+    if steps:
+        assert dX is not None and dU is not None, "dX and dU go together"
+    # (without them: zero rows carried along, never returned)
+    sx = split_phases(dX if steps else np.zeros_like(X), hz, True)
+    su = split_phases(dU if steps else np.zeros_like(U), hz, False)
     for cc in contact_change:
         if hz[0] <= 1:
-            for L in (hz, re, xw, dw, uw):
+            for L in (hz, re, xw, dw, uw, sx, su):
                 L.pop(0)
         else:
-            for L in (xw[0], dw[0], uw[0]):
+            for L in (xw[0], dw[0], uw[0], sx[0], su[0]):
                 L.pop(0)
             hz[0] -= 1
         if cc and re[-1]:
@@ -145,14 +154,20 @@ def shift_working(horizons, reach_end, X, U, Defect, contact_change):
             xw.append([np.zeros_like(X[0]) for _ in range(2)])
             dw.append([np.zeros_like(X[0]) for _ in range(2)])
             uw.append([np.zeros_like(U[0])])
+            sx.append([np.zeros_like(X[0]) for _ in range(2)])
+            su.append([np.zeros_like(U[0])])
         else:
             xw[-1].append(np.array(xw[-1][-1], copy=True))
             dw[-1].append(np.zeros_like(X[0]))
             uw[-1].append(np.zeros_like(U[0]))
+            sx[-1].append(np.zeros_like(X[0]))
+            su[-1].append(np.zeros_like(U[0]))
             hz[-1] += 1
             if cc:
                 re[-1] = 1
     flat = lambda L: np.array([r for ph in L for r in ph])  # noqa: E731
+    if steps:
+        return flat(xw), flat(uw), flat(dw), flat(sx), flat(su)
     return flat(xw), flat(uw), flat(dw)
 
 

@@ -209,6 +209,9 @@ CONSTRAINT_FIELDS = ("reb_delta", "reb_eps", "al_sigma", "al_lambda", "td_mask")
 # Defect: Trajectory, TrajectoryManagement.cpp) and the constraint objects' stored values (GRF g per
 # knot and row, touchdown h per constraint and leg: ConstraintsBase.h:12-55)
 STATE_FIELDS = ("X", "U", "Defect", "grf_g", "td_h")
+# ... and, optional in `state`, the search direction of the previous solve (dX, dU: popped and pushed
+# with their knots, TrajectoryManagement.cpp:137,141,199,203); absent: zero, as a new problem's
+STEP_FIELDS = ("dX", "dU")
 
 
 def solve_batch(prob: dict, options: OrcOptions | None = None, n_threads: int = 1,
@@ -220,7 +223,8 @@ def solve_batch(prob: dict, options: OrcOptions | None = None, n_threads: int = 
     from instead of a new problem's (orc_init_element) — an MPC tick's carried-over ReB / AL
     parameters and touchdown constraints; the outputs carry them after the solve.
     state: STATE_FIELDS ([B] leading axis) to start from instead of a new problem's (X = Xbar,
-    U = Ubar, Defect = 0, zero constraint values) — the previous tick's, shifted (mpc_oracle)."""
+    U = Ubar, Defect = 0, zero constraint values) — the previous tick's, shifted (mpc_oracle);
+    STEP_FIELDS may be given beside them."""
     options = options or default_options()
     B = prob["batch"]
     idx = list(range(B)) if elements is None else list(elements)
@@ -266,7 +270,7 @@ def solve_batch(prob: dict, options: OrcOptions | None = None, n_threads: int = 
             for k in CONSTRAINT_FIELDS:
                 st[k][j] = constraints[k][b]
         if state is not None:
-            for k in STATE_FIELDS:
+            for k in STATE_FIELDS + tuple(f for f in STEP_FIELDS if f in state):
                 st[k][j] = state[k][b]
     hcap = 1 + options.max_AL_iter * options.max_DDP_iter
     hist = np.zeros((n, hcap, 4), np.float32)

@@ -84,6 +84,37 @@ def test_shift_working_follows_the_trajectory_edits():
     assert np.array_equal(Dw[:8], D[4:12]) and not Dw[8:].any()        # pushed state and new phase: zero
 
 
+def test_shift_working_moves_the_search_direction():
+    """dX and dU through mpc_oracle.shift_working, against rows written out by hand: pop_front drops
+    their front rows with the knot, or the whole phase with its last knot (TrajectoryManagement.cpp:
+    137,141), push_back_state appends zero rows (:199,203) and a new phase's are zero (create_data).
+    P = 2, horizons (2, 3): state slots 0-2 | 3-6, control slots 0-1 | 2-4."""
+    horizons, reach = [2, 3], [0, 0]
+    X, U, _ = _traj(horizons, 7)
+    rng = np.random.default_rng(8)
+    D, dX, dU = rng.standard_normal(X.shape), rng.standard_normal(X.shape), rng.standard_normal(U.shape)
+    z = np.zeros(24)
+    # no contact change: knot 0 leaves phase 0, a zero knot joins phase 1 -> (1, 4)
+    out = M.shift_working(horizons, reach, X, U, D, [0], dX=dX, dU=dU)
+    assert len(out) == 5
+    assert np.array_equal(out[3], np.stack([dX[1], dX[2], dX[3], dX[4], dX[5], dX[6], z]))
+    assert np.array_equal(out[4], np.stack([dU[1], dU[2], dU[3], dU[4], z]))
+    # then a contact change: phase 0 (one knot left) leaves whole; the last phase has not reached
+    # its end, so it grows by one more zero knot and is marked -> (5)
+    out = M.shift_working(horizons, reach, X, U, D, [0, 1], dX=dX, dU=dU)
+    assert np.array_equal(out[3], np.stack([dX[3], dX[4], dX[5], dX[6], z, z]))
+    assert np.array_equal(out[4], np.stack([dU[2], dU[3], dU[4], z, z]))
+    # a second change opens a new phase: two zero states, one zero control -> (4, 1)
+    out = M.shift_working(horizons, reach, X, U, D, [0, 1, 1], dX=dX, dU=dU)
+    assert np.array_equal(out[3], np.stack([dX[4], dX[5], dX[6], z, z, z, z]))
+    assert np.array_equal(out[4], np.stack([dU[3], dU[4], z, z, z]))
+    # X, U and Defect are those of the call without dX / dU, which still returns three arrays
+    plain = M.shift_working(horizons, reach, X, U, D, [0, 1, 1])
+    assert len(plain) == 3 and all(np.array_equal(a, b) for a, b in zip(plain, out[:3]))
+    with pytest.raises(AssertionError):
+        M.shift_working(horizons, reach, X, U, D, [0], dX=dX)
+
+
 def test_shift_constraints_carries_stored_values():
     """The constraint objects' stored values follow their knots and constraints (PathConstraintBase::
     pop_front / push_back, ConstraintsBase.h:271-291): a pushed knot's GRF row and a new phase's are
