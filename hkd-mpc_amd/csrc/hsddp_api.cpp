@@ -5,11 +5,13 @@
 // hsddp_settings.cpp.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 
 #include "hsddp_handle.h"
+#include "hsddp_simulate.h"
 
 using namespace hsddp;
 
@@ -220,6 +222,7 @@ extern "C" int hsddp_destroy(hsddp_handle h)
     if (h->ref_table) hipFree(h->ref_table);
     if (h->hist) hipFree(h->hist);
     if (h->value0) hipFree(h->value0);
+    if (h->sim_buf) hipFree(h->sim_buf);
 
     for (auto &g : h->iter_graph)
         if (g.exec) hipGraphExecDestroy(g.exec);
@@ -353,6 +356,7 @@ extern "C" int hsddp_set_element_layouts(hsddp_handle h, const int *n_phases, co
     if ((rc = set_layouts(h, lays))) return rc;
     h->reach_el.assign((size_t)B * HSDDP_MAX_PHASES, 0);  // HKDProblem.cpp:56-57 (quirk A15)
     h->have_problem = false;  // inputs of the new layouts next (hsddp_upload_problem)
+    h->sim_fresh = false;
     h->contacts_current = false;
     h->refs_on_device = false;
     h->ref_cols_stale = true;
@@ -408,6 +412,7 @@ extern "C" int hsddp_set_layout(hsddp_handle h, int n_phases, const int *horizon
     for (int i = 0; i < n_phases; ++i) reach[i] = reach_end && reach_end[i] ? 1 : 0;
     adopt_shared_layout(h, L, reach);
     h->have_problem = false;  // inputs of the new layout next (hsddp_upload_problem)
+    h->sim_fresh = false;
     h->need_inputs = false;
     h->contacts_current = false;
     h->refs_on_device = false;
@@ -415,9 +420,10 @@ extern "C" int hsddp_set_layout(hsddp_handle h, int n_phases, const int *horizon
     return HSDDP_OK;
 }
 
-// contacts, x0 and references of the current layout to the device
+// contacts, x0 and references of the current layout to the device.  x0_dev: x0's rows are on the
+// device, x0_stride doubles apart (hsddp_update_problem_simulated).
 static int upload_inputs(hsddp_handle h, const int *contacts, const double *x0, const double *ref_x,
-                         const double *ref_u, const double *ref_foot)
+                         const double *ref_u, const double *ref_foot, bool x0_dev = false, size_t x0_stride = NX)
 {
     if (!h || !x0) return fail(HSDDP_ERR_ARG, "null argument");
     const bool keep_refs = !ref_x && !ref_u && !ref_foot;
@@ -439,8 +445,11 @@ static int upload_inputs(hsddp_handle h, const int *contacts, const double *x0, 
     for (size_t q = 0; q < B * (P + 1) * 4; ++q)
         if (contacts[q] != 0 && contacts[q] != 1) return fail(HSDDP_ERR_ARG, "contacts must be 0/1");
     int rc;
-    if ((rc = h2d((void *)h->d.contacts, contacts, B * (P + 1) * 4 * sizeof(int), h->stream)) ||
-        (rc = h2d((void *)h->d.x0, x0, B * NX * sizeof(double), h->stream)))
+    if ((rc = h2d((void *)h->d.contacts, contacts, B * (P + 1) * 4 * sizeof(int), h->stream))) return rc;
+    if (x0_dev)
+        HIPCHK(hipMemcpy2DAsync((void *)h->d.x0, NX * sizeof(double), x0, x0_stride * sizeof(double), NX * sizeof(double), B,
+                                hipMemcpyDeviceToDevice, h->stream));
+    else if ((rc = h2d((void *)h->d.x0, x0, B * NX * sizeof(double), h->stream)))
         return rc;
     if (!keep_refs &&
         ((rc = h2d((void *)h->d.ref_x, ref_x, Br * S * NX * sizeof(double), h->stream)) ||
@@ -473,7 +482,7 @@ extern "C" int hsddp_upload_problem(hsddp_handle h, const int *contacts, const d
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_problem = true;
     h->need_inputs = false;
-    return hsddp_upload_warm_start(h, nullptr, nullptr, nullptr);
+    return hsddp_upload_warm_start(h, nullptr, nullptr, nullptr);  // (a new policy: the simulation held is stale)
 }
 
 // params (a new problem: hsddp_upload_warm_start): the working trajectory restarts at the warm
@@ -527,10 +536,113 @@ extern "C" int hsddp_update_problem(hsddp_handle h, const int *contacts, const d
     return reset_working(h, false);
 }
 
+// ---- policy simulation -----------------------------------------------------------------------
+static_assert(sizeof(hsddp_sim_sample) == 32, "hsddp_sim_sample is 32 bytes (include/hsddp.h)");
+
+extern "C" int hsddp_simulate_policy(hsddp_handle h, int n_samples, int n_steps, const double *x_init, double *x_end,
+                                     hsddp_sim_sample *summary, double *X, double *U)
+{
+    if (!h) return fail(HSDDP_ERR_ARG, "null handle");
+    if (!h->have_problem) return fail(HSDDP_ERR_ARG, "upload the problem first");
+    if (h->need_inputs) return fail(HSDDP_ERR_ARG, "the layout changed (hsddp_shift): call hsddp_update_problem first");
+    if (n_samples < 1) return fail(HSDDP_ERR_ARG, "n_samples must be >= 1");
+    if (n_steps < 1 || n_steps > h->p.Kc) return fail(HSDDP_ERR_ARG, "n_steps must lie in 1 .. Kc");
+    if ((X != nullptr) != (U != nullptr)) return fail(HSDDP_ERR_ARG, "X and U: both or neither");
+    const Params &p = h->p;
+    const size_t rows = (size_t)p.B * n_samples;
+    if ((size_t)p.B * (((size_t)n_samples + 63) / 64) > 0x7fffffffu) return fail(HSDDP_ERR_ARG, "too many samples");
+    HIPCHK(hipSetDevice(h->desc.device));
+    // x_end | x_init | summary | X | U, each piece a multiple of 32 bytes
+    const size_t nx = rows * NX * sizeof(double), ns = rows * sizeof(hsddp_sim_sample),
+                 nt = X ? rows * n_steps * NX * sizeof(double) : 0;
+    const size_t need = 2 * nx + ns + 2 * nt;
+    if (need > h->sim_bytes) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->sim_buf) hipFree(h->sim_buf);
+        h->bytes -= h->sim_bytes;
+        h->sim_buf = nullptr;
+        h->sim_bytes = 0;
+        h->sim_M = h->sim_n = 0;  // (the end states held went with the buffer)
+        const hipError_t e = hipMalloc((void **)&h->sim_buf, need);
+        if (e != hipSuccess) {
+            h->sim_buf = nullptr;
+            (void)hipGetLastError();
+            return fail(HSDDP_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
+        }
+        h->sim_bytes = need;
+        h->bytes += need;
+    }
+    SimArgs a{};
+    a.M = n_samples;
+    a.n_steps = n_steps;
+    a.x_end = (double *)h->sim_buf;
+    double *xi = (double *)(h->sim_buf + nx);
+    a.summary = (hsddp_sim_sample *)(h->sim_buf + 2 * nx);
+    if (X) {
+        a.X = (double *)(h->sim_buf + 2 * nx + ns);
+        a.U = (double *)(h->sim_buf + 2 * nx + ns + nt);
+        HIPCHK(hipMemsetAsync(a.X, 0, 2 * nt, h->stream));  // rows past a diverged sample's break knot stay zero
+    }
+    h->sim_M = h->sim_n = 0;  // the held end states are being overwritten
+    int rc;
+    if (x_init) {
+        if ((rc = h2d(xi, x_init, nx, h->stream))) return rc;
+        a.x_init = xi;
+    }
+    // HSDDP_SIMULATE_TIMING=1: the kernel's device time (HIP events) to stderr (a diagnostic)
+    static const bool timing = std::getenv("HSDDP_SIMULATE_TIMING") != nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (timing) {
+        HIPCHK(hipEventCreate(&ev[0]));
+        HIPCHK(hipEventCreate(&ev[1]));
+        HIPCHK(hipEventRecord(ev[0], h->stream));
+    }
+    launch_simulate_policy(p, h->d, a, h->stream);
+    HIPCHK(hipGetLastError());
+    if (timing) {
+        float ms = 0;
+        HIPCHK(hipEventRecord(ev[1], h->stream));
+        HIPCHK(hipEventSynchronize(ev[1]));
+        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        hipEventDestroy(ev[0]);
+        hipEventDestroy(ev[1]);
+        std::fprintf(stderr, "hsddp_simulate_policy kernel ms: %.4f (B %d, M %d, n %d)\n", ms, p.B, n_samples, n_steps);
+    }
+    if (x_end) HIPCHK(hipMemcpyAsync(x_end, a.x_end, nx, hipMemcpyDeviceToHost, h->stream));
+    if (summary) HIPCHK(hipMemcpyAsync(summary, a.summary, ns, hipMemcpyDeviceToHost, h->stream));
+    if (X) {
+        HIPCHK(hipMemcpyAsync(X, a.X, nt, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(U, a.U, nt, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->sim_M = n_samples;
+    h->sim_n = n_steps;
+    h->sim_shifted = 0;
+    h->sim_fresh = true;
+    return HSDDP_OK;
+}
+
+extern "C" int hsddp_update_problem_simulated(hsddp_handle h, int sample)
+{
+    if (!h) return fail(HSDDP_ERR_ARG, "null handle");
+    if (!h->have_problem) return fail(HSDDP_ERR_ARG, "upload the problem first");
+    if (!h->sim_buf || h->sim_M < 1) return fail(HSDDP_ERR_ARG, "no simulation held (hsddp_simulate_policy)");
+    if (!h->sim_fresh) return fail(HSDDP_ERR_ARG, "the simulation held is stale (a solve or warm-start upload since)");
+    if (sample < 0 || sample >= h->sim_M) return fail(HSDDP_ERR_ARG, "sample outside 0 .. n_samples - 1");
+    if (h->sim_shifted != h->sim_n)
+        return fail(HSDDP_ERR_ARG, "the steps advanced since the simulation differ from its n_steps");
+    const double *x0 = (const double *)h->sim_buf + (size_t)sample * NX;
+    int rc = upload_inputs(h, nullptr, x0, nullptr, nullptr, nullptr, true, (size_t)h->sim_M * NX);
+    if (rc) return rc;
+    h->need_inputs = false;
+    return reset_working(h, false);
+}
+
 extern "C" int hsddp_upload_warm_start(hsddp_handle h, const double *Xbar, const double *Ubar, const double *K)
 {
     if (!h) return fail(HSDDP_ERR_ARG, "null handle");
     h->slots_fresh = false;
+    h->sim_fresh = false;
     if (!h->have_problem) return fail(HSDDP_ERR_ARG, "upload the problem first");
     HIPCHK(hipSetDevice(h->desc.device));
     const Params &p = h->p;

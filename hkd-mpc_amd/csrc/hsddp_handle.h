@@ -111,6 +111,14 @@ struct hsddp_handle_t {
     char *cmd_in_host[2] = {nullptr, nullptr};  // pinned staging of each ticket's durations / feet
     size_t cmd_in_bytes[2] = {0, 0};
     int cmd_next = 0;
+    // policy simulation (hsddp_simulate_policy): its device buffers (x_end first, then x_init, the
+    // summaries and the optional X / U rows; grown on demand), and what hsddp_update_problem_simulated
+    // checks: the samples and steps of the simulation held, whether the policy it ran is still the
+    // handle's (no solve or warm-start upload since) and the steps shifted since
+    char *sim_buf = nullptr;
+    size_t sim_bytes = 0;
+    int sim_M = 0, sim_n = 0, sim_shifted = 0;
+    bool sim_fresh = false;
 };
 
 namespace hsddp {

@@ -362,6 +362,7 @@ static int shift_by_flags(hsddp_handle h, int n_steps, const int *cc, size_t bst
     if (plan.phs.size() > 1 && h->Bref == 1 && B > 1)  // checked before any device work: the handle stays usable
         return fail(HSDDP_ERR_ARG, "the elements' shifts diverge into per-element layouts, which need per-element "
                                    "references (ref_per_element = 1)");
+    h->sim_shifted += n_steps;  // (hsddp_update_problem_simulated compares it with the simulation's steps)
     return shift_apply(h, plan, false, nullptr);
 }
 
@@ -623,6 +624,7 @@ static int advance_impl(hsddp_handle h, int n_steps, float plan_duration, float 
     if (!agree && B > 1 && Br == 1)
         return fail(HSDDP_ERR_UNSUPPORTED, "elements disagree on a contact change, which takes per-element layouts "
                                            "and per-element references (ref_per_element = 1)");
+    h->sim_shifted += n_steps;  // (hsddp_update_problem_simulated compares it with the simulation's steps)
     if ((rc = shift_apply(h, plan, agree, &overflow))) return rc;
     stage(1);
     const int P = p.P;  // the new stride (the largest layout's with per-element layouts)

@@ -87,6 +87,7 @@ static int solve_check(hsddp_handle h)
     if (!h->have_problem) return fail(HSDDP_ERR_ARG, "upload the problem first");
     if (h->need_inputs) return fail(HSDDP_ERR_ARG, "the layout changed (hsddp_shift): call hsddp_update_problem first");
     HIPCHK(hipSetDevice(h->desc.device));
+    h->sim_fresh = false;  // the policy changes: a simulation held is of the old one
     return HSDDP_OK;
 }
 

@@ -8,6 +8,11 @@
 //   update()                          HKDProblem::update + re-solve with max_AL_iter = 2,
 //                                     max_DDP_iter = 1 + update_foot_placement + publish_mpc_cmd
 //                                     (HKDMPC.cpp:96-165, 207-298)
+//   simulate_policy(...)              the solved policy simulated from given states
+//                                     (hsddp_simulate_policy)
+//   update_closed_loop()              update() with the plant on the device: the next initial state
+//                                     is the policy's own simulation of the steps between two updates
+//                                     (closed_loop = true makes the message handler run it)
 //
 // Device-side: the phase bookkeeping, warm-start shift, per-knot references, solve and command
 // extraction (hsddp_advance, hsddp_solve, hsddp_extract_commands); per tick only the B robot
@@ -142,7 +147,8 @@ public:
         }
         worker = std::thread([this] {
             try {
-                update();
+                if (closed_loop) update_closed_loop();
+                else update();
             } catch (...) {
                 worker_error = std::current_exception();
             }
@@ -207,6 +213,51 @@ public:
         if (publish) publish(commands);
     }
 
+    // hsddp_simulate_policy for the batch: n_samples states per robot, n_steps knots each (x_init
+    // [B][n_samples][24] or null: the robots' current x0; outputs may be null)
+    void simulate_policy(int n_samples, int n_steps, const double *x_init, double *x_end, hsddp_sim_sample *summary,
+                         double *X = nullptr, double *U = nullptr)
+    {
+        chk(hsddp_simulate_policy(h, n_samples, n_steps, x_init, x_end, summary, X, U));
+    }
+
+    // update() with the plant in the loop: the policy of the last solve is simulated for the
+    // nsteps_between_mpc steps from the handle's x0 (one sample per robot), the problem advances
+    // with its inputs pending, and the simulation's end states become the new initial states on
+    // the device (hsddp_update_problem_simulated: no FK round trip, no x0 upload).  The messages
+    // still give mpctime and the current foot placements.
+    void update_closed_loop()
+    {
+        std::lock_guard<std::mutex> lk(mpc_mutex);
+        hsddp_options o = ddp_options;
+        o.max_AL_iter = 2;  // quirk A17
+        o.max_DDP_iter = 1;
+        chk(hsddp_set_options(h, &o));
+        mpc_iter++;
+        const int n = mpc_config.nsteps_between_mpc;
+        plant.resize(B);
+        chk(hsddp_simulate_policy(h, 1, n, nullptr, nullptr, plant.data(), nullptr, nullptr));
+        std::vector<int> flags(n);
+        chk(hsddp_advance(h, n, mpc_config.plan_duration, dt_mpc, nullptr, flags.data()));
+        int hz[HSDDP_MAX_PHASES];
+        chk(hsddp_get_layout(h, &P, hz, nullptr, nullptr));
+        durations.assign((size_t)B * P * 4, 0.0);
+        chk(hsddp_get_phase_info(h, nullptr, durations.data()));
+        chk(hsddp_update_problem_simulated(h, 0));
+        const auto t0 = std::chrono::high_resolution_clock::now();
+        hsddp_stats st;
+        chk(hsddp_solve(h, &st));
+        const auto t1 = std::chrono::high_resolution_clock::now();
+        solve_time = (float)std::chrono::duration<double, std::milli>(t1 - t0).count();
+        std::vector<float> pf((size_t)B * 12);
+        for (int b = 0; b < B; ++b)
+            for (int j = 0; j < 12; ++j) pf[(size_t)b * 12 + j] = hkd_data[b].foot_placements[j];
+        commands.resize(B);
+        chk(hsddp_extract_commands(h, n, mpc_time, dt_mpc, durations.data(), 1, pf.data(), 1, solve_time,
+                                   commands.data()));
+        if (publish) publish(commands);
+    }
+
     // per-element results of the last solve
     std::vector<hsddp_element_info> solver_info() const
     {
@@ -224,6 +275,8 @@ public:
     std::vector<hkd_data_lcmt> hkd_data;
     std::vector<hsddp_mpc_command> commands;
     std::vector<double> durations;
+    bool closed_loop = false;              // the message handler runs update_closed_loop()
+    std::vector<hsddp_sim_sample> plant;   // the plant's outcome per robot in the last closed-loop update
     double mpc_time = 0, mpc_time_prev = 0;
     float solve_time;
     int mpc_iter = 0, P = 0;

@@ -4,7 +4,9 @@
 // The robot states are a deterministic synthetic stream (float arithmetic only, reproducible in
 // any language); the commands are written out for comparison.
 //
-//   hkd_mpc_example <quad_reference.csv> <ddp_setting.info> <out_dir> <batch> <ticks>
+//   hkd_mpc_example <quad_reference.csv> <ddp_setting.info> <out_dir> <batch> <ticks> [closed]
+//   closed: every tick's initial state is the policy's own simulation on the device
+//           (HKDMPCSolver::update_closed_loop) instead of the message's robot state
 //   writes <out_dir>/commands.bin: ticks x batch hsddp_mpc_command records,
 //          <out_dir>/layout.txt:   per tick the horizons and the solve time (ms)
 #include <cstdio>
@@ -39,13 +41,18 @@ static hkd::hkd_data_lcmt message(int t, int b)
 int main(int argc, char **argv)
 {
     if (argc < 6) {
-        std::cerr << "usage: hkd_mpc_example <quad_reference.csv> <ddp_setting.info> <out_dir> <batch> <ticks>\n";
+        std::cerr << "usage: hkd_mpc_example <quad_reference.csv> <ddp_setting.info> <out_dir> <batch> <ticks> [closed]\n";
         return 2;
     }
     try {
         const std::string out = argv[3];
         const int B = std::atoi(argv[4]), ticks = std::atoi(argv[5]);
+        if (argc > 6 && std::string(argv[6]) != "closed") {
+            std::cerr << "hkd_mpc_example: unknown mode " << argv[6] << "\n";
+            return 2;
+        }
         hkd::HKDMPCSolver mpc(argv[1], B, argv[2]);
+        mpc.closed_loop = argc > 6;
         std::ofstream cf(out + "/commands.bin", std::ios::binary), lf(out + "/layout.txt");
         mpc.set_publisher([&](const std::vector<hsddp_mpc_command> &cmds) {
             cf.write((const char *)cmds.data(), (std::streamsize)(cmds.size() * sizeof(hsddp_mpc_command)));

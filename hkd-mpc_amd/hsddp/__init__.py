@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from . import model, synthetic  # noqa: F401
-from ._lib import (MPC_COMMAND, PHASE_PLAN, QUAD_STATE, ConstraintParams, ElementInfo, HSDDPError, Options, ProblemDesc, Stats, Weights,
+from ._lib import (MPC_COMMAND, PHASE_PLAN, QUAD_STATE, SIM_SAMPLE, ConstraintParams, ElementInfo, HSDDPError, Options, ProblemDesc, Stats, Weights,
                    check, dp, ip, lib)
 
 SETTINGS_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "settings")
@@ -451,6 +451,44 @@ class Solver:
         self._follow_layout()
         check(rc)
         return [int(f) for f in flags[:n_steps]]
+
+    # -- policy simulation (hsddp_simulate_policy) ---------------------------------------------
+    def simulate_policy(self, x_init=None, n_steps: int = 1, n_samples: int | None = None,
+                        trajectories: bool = False) -> dict:
+        """The solved policy U = Ubar + K (X - Xbar) simulated for n_steps knots from M states per
+        element (SinglePhase::hybrid_rollout's simulated branch at eps = 0, with the reset maps
+        between phases).  x_init [B][M][24] (None: n_samples copies of the element's x0, one by
+        default).  Returns x_end [B][M][24], summary [B][M] SIM_SAMPLE records (cost, min_grf,
+        max_td, steps, status) and, with trajectories, X, U [B][M][n_steps][24] (lane-strided
+        stores on the device: for inspection).  The end states stay on the device for
+        update_problem_simulated."""
+        if x_init is None:
+            M = 1 if n_samples is None else int(n_samples)
+            xi = None
+        else:
+            xi = np.ascontiguousarray(x_init, dtype=np.float64)
+            if xi.ndim != 3 or xi.shape[0] != self.B or xi.shape[2] != 24:
+                raise HSDDPError(f"x_init: shape {xi.shape}, expected ({self.B}, M, 24)")
+            M = xi.shape[1]
+            if n_samples is not None and int(n_samples) != M:
+                raise HSDDPError(f"x_init: shape {xi.shape}, expected ({self.B}, {int(n_samples)}, 24)")
+        n = int(n_steps)
+        Ma, na = max(M, 0), max(n, 0)  # (the C side refuses the counts; no array is read then)
+        out = {"x_end": np.zeros((self.B, Ma, 24)), "summary": np.zeros((self.B, Ma), dtype=SIM_SAMPLE)}
+        if trajectories:
+            out["X"] = np.zeros((self.B, Ma, na, 24))
+            out["U"] = np.zeros((self.B, Ma, na, 24))
+        check(lib().hsddp_simulate_policy(self._h, M, n, None if xi is None else xi.ctypes.data,
+                                          out["x_end"].ctypes.data, out["summary"].ctypes.data,
+                                          out["X"].ctypes.data if trajectories else None,
+                                          out["U"].ctypes.data if trajectories else None))
+        return out
+
+    def update_problem_simulated(self, sample: int = 0) -> None:
+        """update_problem(None, x0) with x0[b] = the end state of `sample` of the last
+        simulate_policy, copied on the device (after advance(None, n_steps) of the same steps)."""
+        check(lib().hsddp_update_problem_simulated(self._h, int(sample)))
+        self._contacts = None
 
     def phase_info(self) -> dict:
         """contacts [B][P+1][4] (row P: the last phase's next contact); durations [B][P][4] when the

@@ -74,6 +74,12 @@ MPC_COMMAND = np.dtype([("N_mpcsteps", np.int32), ("mpc_times", np.float64, (10,
                         ("solve_time", np.float32)], align=True)
 
 
+# hsddp_sim_sample (include/hsddp.h): one simulated sample's outcome (tests/test_simulate_host.py
+# checks size and offsets against the C compiler)
+SIM_SAMPLE = np.dtype([("cost", np.float64), ("min_grf", np.float64), ("max_td", np.float64),
+                       ("steps", np.int32), ("status", np.int32)], align=True)
+
+
 # hsddp_quad_state (QuadAugmentedState) and hsddp_phase_plan (include/hsddp.h) as C-aligned records
 QUAD_STATE = np.dtype([("body_state", np.float64, (12,)), ("qJ", np.float64, (12,)), ("qJd", np.float64, (12,)),
                        ("foot_placements", np.float64, (12,)), ("grf", np.float64, (12,)),
@@ -109,6 +115,7 @@ EXPORTS = [
     "hsddp_set_layout", "hsddp_upload_constraint_params", "hsddp_download_constraint_params",
     "hsddp_download_constraint_values",
     "hsddp_extract_commands_async", "hsddp_commands_wait",
+    "hsddp_simulate_policy", "hsddp_update_problem_simulated",
 ]
 
 
@@ -189,6 +196,8 @@ def lib():
     L.hsddp_extract_commands_async.argtypes = [V, C.c_int, C.c_double, C.c_double, V, C.c_int, V, C.c_int, C.c_float,
                                                C.POINTER(C.c_int)]
     L.hsddp_commands_wait.argtypes = [V, C.c_int, C.POINTER(C.c_void_p)]
+    L.hsddp_simulate_policy.argtypes = [V, C.c_int, C.c_int, V, V, V, V, V]
+    L.hsddp_update_problem_simulated.argtypes = [V, C.c_int]
     _lib = L
     return L
 

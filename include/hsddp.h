@@ -32,6 +32,8 @@
  *   hsddp_set_layout                          a caller-side HKDProblem::update's layout + SinglePhase::
  *                                             update_SS_config (SS_set)  HKDProblem.cpp:203-217; SinglePhase.h:161-164
  *   hsddp_extract_commands(_async)            update_foot_placement + publish_mpc_cmd HKDMPC.cpp:207-298
+ *   hsddp_simulate_policy                     SinglePhase::hybrid_rollout's simulated branch at eps = 0 +
+ *                                             MultiPhaseDDP::hybrid_rollout's reset  SinglePhase.cpp:196-222; MultiPhaseDDP.cpp:73-81
  *   hsddp_hkd_dynamics                        HKD::Model::dynamics (hkinodyn)       HKDModel.h:33-45
  *   hsddp_hkd_dynamics_partial                HKD::Model::dynamics_partial          HKDModel.h:46-61
  *   hsddp_hkd_resetmap(_partial)              HKDReset::resetmap(_partial)          HKDReset.h:41-136
@@ -439,6 +441,59 @@ int hsddp_extract_commands_device(hsddp_handle h, int nsteps_between_mpc, double
                                   const double *status_durations, int durations_per_element,
                                   const float *foot_placements, int feet_per_element, float solve_time,
                                   void *out_device);
+
+/* ---- policy simulation: the plant of the MPC loop, Monte-Carlo evaluation ---------------------
+ * The simulated branch of SinglePhase::hybrid_rollout at eps = 0 (SinglePhase.cpp:196-222) with
+ * MultiPhaseDDP::hybrid_rollout's reset map between phases (MultiPhaseDDP.cpp:73-81), applied to
+ * the solved policy (Xbar, Ubar, K as hsddp_download_trajectory returns them) from states the
+ * caller names: n_samples states per element, n_steps knots each. */
+typedef struct hsddp_sim_sample {
+    double cost;      /* sum of running costs of the simulated knots + Phi of every phase end reached; no ReB, no AL */
+    double min_grf;   /* min over simulated knots, stance legs and the 5 pyramid rows of g = A_leg f; +inf if none */
+    double max_td;    /* max |foot z - ground_height| over the touchdown legs of the phase ends reached; 0 if none */
+    int steps;        /* knots simulated (n_steps unless status != 0) */
+    int status;       /* 0 ok, 1 diverged */
+} hsddp_sim_sample;   /* 32 bytes */
+
+/* For element b and sample m, on b's own layout (phase i: N_i knots, contact rows c_i, c_{i+1}):
+ *     x = x_init[b][m]; cost = 0; min_grf = +inf; max_td = 0; steps = 0; status = 0
+ *     for j = 0 .. n_steps - 1:                 control knot kc = j = k0_i + k, state slot s = s0_i + k
+ *         u = Ubar[kc] + K[kc] (x - Xbar[s])    (the fp32 gains widened on a riccati_fp32 handle)
+ *         X[b][m][j] = x; U[b][m][j] = u
+ *         xs = hkinodyn(x, u, dt, c_i)
+ *         if !(||xs||_2 <= 1e6): status = 1; break     (SinglePhase.cpp:205-208; a NaN counts as diverged too)
+ *         cost += l(x, u; references of slot s, c_i)   (hsddp_hkd_running_cost, terms TRACKING | FOOT)
+ *         min_grf = min(min_grf, rows of A_leg u of the stance legs of c_i)
+ *         steps = j + 1; x = xs
+ *         if k == N_i - 1:                             (x is X_i[N_i])
+ *             cost += Phi(x; references of slot s0_i + N_i, c_i)     (hsddp_hkd_terminal_cost)
+ *             max_td = max(max_td, |foot_z(x, l) - ground_height|, legs l with c_i[l] = 0, c_{i+1}[l] = 1)
+ *             if i + 1 < P_b: x = resetmap(x, c_i, c_{i+1})
+ *     x_end[b][m] = x
+ * So when the last step ends a phase that has a successor, x_end has already passed through the
+ * reset map: it is expressed in the contact of knot n_steps, the first knot after an hsddp_advance
+ * of n_steps.  After the last phase there is no reset.  On divergence x_end is the last accepted
+ * state, and the rows of X, U past `steps` are zero except the break knot's own row.
+ * x_init [B][M][24] (NULL: every sample starts at the element's x0); x_end [B][M][24], summary
+ * [B][M], X, U [B][M][n_steps][24] (any may be NULL; X and U both or neither).  X and U are written
+ * one row per lane — strided, uncoalesced stores: they are for inspection, not for the hot path.
+ * HSDDP_ERR_ARG: n_samples < 1, n_steps outside 1 .. Kc, no problem uploaded, a shift awaiting
+ * hsddp_update_problem.  The call reads the handle's state and writes only its own buffers: a
+ * solve, shift or extraction afterwards gives the same bits as if it had not happened.  Its device
+ * buffers are allocated on first use and only grow, are counted by hsddp_device_bytes and freed by
+ * hsddp_destroy; an allocation that fails returns HSDDP_ERR_ALLOC and leaves the handle usable.
+ * Runs on the handle's stream and returns after the outputs have arrived.  The end states stay on
+ * the device, and the handle remembers n_samples, n_steps and that no solve or warm-start upload
+ * has happened since (hsddp_update_problem_simulated). */
+int hsddp_simulate_policy(hsddp_handle h, int n_samples, int n_steps, const double *x_init, double *x_end,
+                          hsddp_sim_sample *summary, double *X, double *U);
+/* hsddp_update_problem(h, NULL, x0, NULL, NULL, NULL) with x0[b] = the end state of sample `sample`
+ * of the last hsddp_simulate_policy, taken from its device copy (no host round trip): the closed
+ * MPC loop is hsddp_simulate_policy(n), hsddp_advance(n, .., x0 = NULL, ..), this call, hsddp_solve.
+ * HSDDP_ERR_ARG: no simulation held, or a solve or warm-start upload since (stale); sample outside
+ * 0 .. n_samples - 1; the steps advanced or shifted since the simulation differ from its n_steps;
+ * no contacts of the current layout on the handle. */
+int hsddp_update_problem_simulated(hsddp_handle h, int sample);
 
 /* ---- batched model primitives (device pointers, n points, async on `stream` (NULL = default)) */
 /* xn[n][24] = hkinodyn(x[n][24], u[n][24], dt, c[n][4]) */

@@ -7,6 +7,11 @@ hsddp_extract_commands (k_extract_commands).  Every C-ABI call returns synchroni
 wall-clock split is per stage; kernel durations come from rocprofv3 over the same script.
 
     python tools/mpc_bench.py [--batch B] [--ticks T]     -> one JSON line
+
+--closed-loop puts the plant on the device: each tick's x0 is the solved policy simulated for the
+tick's step (hsddp_simulate_policy, one sample per robot), handed over by
+hsddp_update_problem_simulated after an advance with pending inputs; the plant's time per tick
+is reported beside advance (which then includes that hand-over) and solve.
 """
 import argparse
 import json
@@ -29,6 +34,8 @@ def main():
     ap.add_argument("--sync", action="store_true",
                     help="synchronous extraction into pageable memory (round 3's path) instead of the "
                          "asynchronous copy into the handle's pinned buffers")
+    ap.add_argument("--closed-loop", action="store_true",
+                    help="x0 of every tick from the policy simulated on the device instead of host noise")
     args = ap.parse_args()
     B = args.batch
     tab, dt = hsddp.load_quad_reference(os.path.join(ROOT, "tests", "golden", "ref_trot.csv"))
@@ -42,13 +49,23 @@ def main():
     s.solve()
     s.set_options(hsddp.load_settings(max_AL_iter=2, max_DDP_iter=1))
     feet = np.tile(np.float32([.2, -.14, 0, .2, .14, 0, -.2, -.14, 0, -.2, .14, 0]), (B, 1))
-    t_adv, t_solve, t_cmd = [], [], []
+    t_adv, t_solve, t_cmd, t_plant = [], [], [], []
+    plant_ok = True
     flags = 0
     ticket, cmd, t_last = None, None, 0.0
     for it in range(args.ticks):
-        xt = x0 + rng.uniform(-.01, .01, x0.shape)
-        t0 = time.perf_counter()
-        flags += sum(s.advance(xt, 1))
+        if args.closed_loop:
+            tp = time.perf_counter()
+            plant = s.simulate_policy(None, 1)
+            t0 = time.perf_counter()
+            t_plant.append(t0 - tp)
+            plant_ok = plant_ok and bool(np.all(plant["summary"]["status"] == 0))
+            flags += sum(s.advance(None, 1))
+            s.update_problem_simulated(0)
+        else:
+            xt = x0 + rng.uniform(-.01, .01, x0.shape)
+            t0 = time.perf_counter()
+            flags += sum(s.advance(xt, 1))
         t1 = time.perf_counter()
         s.solve()
         t2 = time.perf_counter()
@@ -81,6 +98,10 @@ def main():
            "last_copy_wait_ms": t_last * 1e3,
            "robot_ticks_per_s": B / (np.median(t_adv) + np.median(t_solve) + np.median(t_cmd)),
            "shift_gather_algorithmic_bytes": shift_bytes, "all_finite": finite}
+    if args.closed_loop:
+        out["metric"] = "closed-loop MPC tick (plant + advance + solve + extract), HKD trot reference file"
+        out["ms_per_tick_median"]["plant"] = med(t_plant)
+        out["plant_all_ok"] = plant_ok
     print(json.dumps(out), flush=True)
     s.close()
 
