@@ -854,6 +854,19 @@ DEV int sweep_pair(const Params &p, const Bufs &d, LdsT &S, const Lane &L, const
     return it.act ? fail : -1;
 }
 
+constexpr int STAGE_SLOTS = 512;  // slots the staging pass covers: 16 loads per lane and array
+
+// The staging area for a handle of p.S slots: `item` (free until the sweep starts) if two arrays of
+// p.S doubles fit it and the staging pass covers them, else nullptr.  Staged up to p.S = 509 in
+// the fp64 one-wave sweep (item of 8144 bytes), 254 in fp32 (4072 bytes) and STAGE_SLOTS in the
+// column split (13344 bytes would hold 834: the pass decides).
+template <typename ItemT>
+DEV double *cost_stage(const Params &p, ItemT &item)
+{
+    const bool fits = p.S <= STAGE_SLOTS && 2 * (size_t)p.S * sizeof(double) <= sizeof(ItemT);
+    return fits ? reinterpret_cast<double *>(&item) : nullptr;
+}
+
 // ElemState cost / feasibility of element b at the start of the inner iteration
 // (MultiPhaseDDP.cpp:306-307; the reference's summation order): the half-wave's 32 lanes stage the
 // element's slot costs and |Defect|^2 in `stg` (the item's LDS, not yet in use; every load in flight
@@ -866,10 +879,10 @@ DEV void element_cost(const Params &p, const Bufs &d, int b, int lane, double *s
     const auto LY = layout_of<EL>(d, b);
     const int P = LY.P(), g = lane & 31;
     const double *c = d.slot_cost + (size_t)b * p.S, *f = d.slot_feas + (size_t)b * p.S;
-    if (stg) {  // (p.S <= 512: the fp64 item holds two arrays of 509)
+    if (stg) {  // (cost_stage: p.S <= 509 in the fp64 one-wave sweep, 254 in fp32, 512 in the split)
         const int Sel = LY.S();
 #pragma unroll
-        for (int t = 0; t < 16; ++t) {
+        for (int t = 0; t < STAGE_SLOTS / 32; ++t) {
             const int sl = g + 32 * t;
             if (sl < Sel) {
                 stg[sl] = c[sl];
@@ -978,7 +991,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB ==
     double ecost, efeas;
     {
         // the slot values staged in this item's LDS (free until the sweep starts), two arrays of p.S
-        double *stg = 2 * (size_t)p.S * sizeof(double) <= sizeof(S.it[0]) ? reinterpret_cast<double *>(&S.it[L.e]) : nullptr;
+        double *stg = cost_stage(p, S.it[L.e]);
         element_cost<EL>(p, d, bv, L.lane, stg, ecost, efeas);
         SSYNC();
     }
@@ -1060,7 +1073,7 @@ DEV void riccati_cs_wave(const Params &p, const Bufs &d, LdsCS<double> &S)
     if (!__builtin_amdgcn_ballot_w64(act)) return;
     double ecost = 0, efeas = 0;
     if (W == 0) {
-        double *stg = 2 * (size_t)p.S * sizeof(double) <= sizeof(S.it[0]) ? reinterpret_cast<double *>(&S.it[L.e]) : nullptr;
+        double *stg = cost_stage(p, S.it[L.e]);
         element_cost<EL>(p, d, bv, L.lane, stg, ecost, efeas);
     }
     CSYNC();  // (the staging area is the item's images)
