@@ -5,12 +5,14 @@
 // hsddp_settings.cpp.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 
 #include "hsddp_handle.h"
+#include "hsddp_measure.h"
 #include "hsddp_simulate.h"
 
 using namespace hsddp;
@@ -420,12 +422,35 @@ extern "C" int hsddp_set_layout(hsddp_handle h, int n_phases, const int *horizon
     return HSDDP_OK;
 }
 
-// contacts, x0 and references of the current layout to the device.  x0_dev: x0's rows are on the
-// device, x0_stride doubles apart (hsddp_update_problem_simulated).
-static int upload_inputs(hsddp_handle h, const int *contacts, const double *x0, const double *ref_x,
-                         const double *ref_u, const double *ref_foot, bool x0_dev = false, size_t x0_stride = NX)
+// hsddp_update_problem_measured's records: [B] on the host (on_device = 0) or on the handle's device
+struct Measured {
+    const hsddp_robot_state *states;
+    int on_device;
+};
+
+// a buffer of the measured-state ingest, allocated at its first use: counted by hsddp_device_bytes
+// and freed with the handle; a failed allocation leaves the handle as it was
+template <typename T>
+static int measured_alloc(hsddp_handle h, T *&ptr, size_t n)
 {
-    if (!h || !x0) return fail(HSDDP_ERR_ARG, "null argument");
+    if (ptr) return HSDDP_OK;
+    const int rc = dalloc(h, ptr, n);
+    if (rc) {
+        ptr = nullptr;
+        (void)hipGetLastError();
+    }
+    return rc;
+}
+
+// contacts, x0 and references of the current layout to the device.  x0_dev: x0's rows are on the
+// device, x0_stride doubles apart (hsddp_update_problem_simulated).  meas: x0 is formed on the
+// device from the measured records, behind the contacts' copy, and the handle keeps the records'
+// foot placements (hsddp_update_problem_measured); every other x0 drops the ones it held.
+static int upload_inputs(hsddp_handle h, const int *contacts, const double *x0, const double *ref_x,
+                         const double *ref_u, const double *ref_foot, bool x0_dev = false, size_t x0_stride = NX,
+                         const Measured *meas = nullptr)
+{
+    if (!h || (!x0 && !meas)) return fail(HSDDP_ERR_ARG, "null argument");
     const bool keep_refs = !ref_x && !ref_u && !ref_foot;
     if (!keep_refs && (!ref_x || !ref_u || !ref_foot)) return fail(HSDDP_ERR_ARG, "references: all three or none");
     if (keep_refs && !h->refs_on_device)
@@ -445,12 +470,28 @@ static int upload_inputs(hsddp_handle h, const int *contacts, const double *x0, 
     for (size_t q = 0; q < B * (P + 1) * 4; ++q)
         if (contacts[q] != 0 && contacts[q] != 1) return fail(HSDDP_ERR_ARG, "contacts must be 0/1");
     int rc;
+    if (meas && ((!meas->on_device && (rc = measured_alloc(h, h->meas_states, B))) ||
+                 (rc = measured_alloc(h, h->meas_feet, B * 12))))
+        return rc;
     if ((rc = h2d((void *)h->d.contacts, contacts, B * (P + 1) * 4 * sizeof(int), h->stream))) return rc;
-    if (x0_dev)
+    if (meas) {
+        const hsddp_robot_state *ds = meas->states;
+        if (!meas->on_device) {
+            if ((rc = h2d(h->meas_states, meas->states, B * sizeof(hsddp_robot_state), h->stream))) return rc;
+            ds = h->meas_states;
+        }
+        launch_hkd_state(ds, h->d.contacts, (int)(P + 1) * 4, (double *)h->d.x0, (int)B, h->stream);
+        HIPCHK(hipGetLastError());
+        // the feet: 48 of every 144 bytes
+        h->meas_held = false;
+        HIPCHK(hipMemcpy2DAsync(h->meas_feet, 12 * sizeof(float), (const char *)ds + offsetof(hsddp_robot_state, foot_placements),
+                                sizeof(hsddp_robot_state), 12 * sizeof(float), B, hipMemcpyDeviceToDevice, h->stream));
+    } else if (x0_dev)
         HIPCHK(hipMemcpy2DAsync((void *)h->d.x0, NX * sizeof(double), x0, x0_stride * sizeof(double), NX * sizeof(double), B,
                                 hipMemcpyDeviceToDevice, h->stream));
     else if ((rc = h2d((void *)h->d.x0, x0, B * NX * sizeof(double), h->stream)))
         return rc;
+    h->meas_held = meas != nullptr;
     if (!keep_refs &&
         ((rc = h2d((void *)h->d.ref_x, ref_x, Br * S * NX * sizeof(double), h->stream)) ||
          (rc = h2d((void *)h->d.ref_u, ref_u, Br * S * NX * sizeof(double), h->stream)) ||
@@ -534,6 +575,50 @@ extern "C" int hsddp_update_problem(hsddp_handle h, const int *contacts, const d
     // resets the per-element solver state; touchdown constraints added by the shift take their legs
     // from the new contact rows
     return reset_working(h, false);
+}
+
+static_assert(sizeof(hsddp_robot_state) == 144 && offsetof(hsddp_robot_state, foot_placements) == 96,
+              "hsddp_robot_state is 144 bytes, the feet its last 48 (include/hsddp.h)");
+
+// records [n] readable on `device`: what the HIP runtime knows of the pointer
+static int check_device_records(const void *ptr, size_t n, int device)
+{
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(HSDDP_ERR_ARG, "states: not a device pointer");
+    }
+    if ((at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != device)
+        return fail(HSDDP_ERR_ARG, "states: not device memory of the handle's device");
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(HSDDP_ERR_ARG, "states: not a device allocation");
+    }
+    const size_t off = (size_t)((const char *)ptr - (const char *)base);
+    if (off > size || n * sizeof(hsddp_robot_state) > size - off)
+        return fail(HSDDP_ERR_ARG, "states: the device allocation holds fewer than B records");
+    return HSDDP_OK;
+}
+
+extern "C" int hsddp_update_problem_measured(hsddp_handle h, const int *contacts, const hsddp_robot_state *states,
+                                             int states_on_device, const double *ref_x, const double *ref_u,
+                                             const double *ref_foot)
+{
+    if (!h) return fail(HSDDP_ERR_ARG, "null handle");
+    if (!h->have_problem) return fail(HSDDP_ERR_ARG, "upload the problem first");
+    if (!states) return fail(HSDDP_ERR_ARG, "null argument");
+    if (states_on_device != 0 && states_on_device != 1) return fail(HSDDP_ERR_ARG, "states_on_device must be 0 or 1");
+    if (states_on_device) {
+        HIPCHK(hipSetDevice(h->desc.device));
+        if (int rc = check_device_records(states, (size_t)h->p.B, h->desc.device)) return rc;
+    }
+    const Measured meas{states, states_on_device};
+    int rc = upload_inputs(h, contacts, nullptr, ref_x, ref_u, ref_foot, false, NX, &meas);
+    if (rc) return rc;
+    h->need_inputs = false;
+    return reset_working(h, false);  // (as hsddp_update_problem; its synchronisation ends the reads of `states`)
 }
 
 // ---- policy simulation -----------------------------------------------------------------------
@@ -1099,6 +1184,12 @@ extern "C" int hsddp_hkd_foot_position(const double *x, const int *leg, double *
 {
     if (!x || !leg || !p || n < 0) return fail(HSDDP_ERR_ARG, "bad argument");
     if (n) launch_model_foot(x, leg, p, nullptr, n, (hipStream_t)stream);
+    return check_launch();
+}
+extern "C" int hsddp_hkd_state(const hsddp_robot_state *states, const int *contact, double *x, int n, void *stream)
+{
+    if (!states || !contact || !x || n < 0) return fail(HSDDP_ERR_ARG, "bad argument");
+    if (n) launch_hkd_state(states, contact, 4, x, n, (hipStream_t)stream);
     return check_launch();
 }
 extern "C" int hsddp_hkd_foot_jacobian(const double *x, const int *leg, double *J, int n, void *stream)

@@ -119,6 +119,13 @@ struct hsddp_handle_t {
     size_t sim_bytes = 0;
     int sim_M = 0, sim_n = 0, sim_shifted = 0;
     bool sim_fresh = false;
+    // measured states (hsddp_update_problem_measured): the device copy of records that came from the
+    // host [B], the handle's own copy of the records' foot placements [B][12] (both allocated on
+    // first use), and whether that copy belongs to the current tick (an update with a host-formed or
+    // simulated x0 drops it)
+    hsddp_robot_state *meas_states = nullptr;
+    float *meas_feet = nullptr;
+    bool meas_held = false;
 };
 
 namespace hsddp {

@@ -22,10 +22,22 @@ using namespace hsddp;
 static int extract_commands(hsddp_handle h, int nsteps_between_mpc, double mpc_time, double dt_mpc,
                             const double *status_durations, int durations_per_element, const float *foot_placements,
                             int feet_per_element, float solve_time, hsddp_mpc_command *out, bool out_on_device,
-                            int ticket = -1)
+                            int ticket = -1, bool measured = false)
 {
     if (!h || (!out && ticket < 0)) return fail(HSDDP_ERR_ARG, "null argument");
     if (!h->have_problem) return fail(HSDDP_ERR_ARG, "upload the problem first");
+    if (measured) {
+        // the feet are the handle's device copy of the measured records', per element; NULL durations
+        // are the handle's own when the references were built from a table (hsddp_get_phase_info's)
+        if (!h->meas_held || !h->meas_feet)
+            return fail(HSDDP_ERR_ARG, "no measured states held for this tick (hsddp_update_problem_measured)");
+        foot_placements = nullptr;
+        feet_per_element = 1;
+        if (!status_durations && h->durations.size() == (size_t)h->p.B * h->p.P * 4) {
+            status_durations = h->durations.data();
+            durations_per_element = 1;
+        }
+    }
     const Params &p = h->p;
     CmdArgs a{};
     a.n = nsteps_between_mpc + 7;  // HKDMPC.cpp:232-233
@@ -85,6 +97,7 @@ static int extract_commands(hsddp_handle h, int nsteps_between_mpc, double mpc_t
         a.feet = (const float *)(buf + cmd_bytes + dur_bytes);
         if ((rc = h2d((void *)a.feet, feet_src, feet_bytes, h->stream))) return rc;
     }
+    if (measured) a.feet = h->meas_feet;
     if (ticket >= 0)  // the buffer's previous copy (two extractions ago) has left it
         HIPCHK(hipStreamWaitEvent(h->stream, h->cmd_copied[ticket], 0));
     launch_extract_commands(p, h->d, a, dcmd, h->stream);
@@ -118,6 +131,14 @@ extern "C" int hsddp_extract_commands_device(hsddp_handle h, int nsteps_between_
 {
     return extract_commands(h, nsteps_between_mpc, mpc_time, dt_mpc, status_durations, durations_per_element,
                             foot_placements, feet_per_element, solve_time, (hsddp_mpc_command *)out_device, true);
+}
+
+extern "C" int hsddp_extract_commands_measured(hsddp_handle h, int nsteps_between_mpc, double mpc_time, double dt_mpc,
+                                               const double *status_durations, int durations_per_element,
+                                               float solve_time, hsddp_mpc_command *out, int out_on_device)
+{
+    return extract_commands(h, nsteps_between_mpc, mpc_time, dt_mpc, status_durations, durations_per_element, nullptr,
+                            1, solve_time, out, out_on_device != 0, -1, true);
 }
 
 extern "C" int hsddp_extract_commands_async(hsddp_handle h, int nsteps_between_mpc, double mpc_time, double dt_mpc,

@@ -14,9 +14,10 @@
 //                                     is the policy's own simulation of the steps between two updates
 //                                     (closed_loop = true makes the message handler run it)
 //
-// Device-side: the phase bookkeeping, warm-start shift, per-knot references, solve and command
-// extraction (hsddp_advance, hsddp_solve, hsddp_extract_commands); per tick only the B robot
-// states go up and the B commands come back.  LCM is not available on this platform: a message
+// Device-side: the phase bookkeeping, warm-start shift, per-knot references, the initial state from
+// the measured robot states, solve and command extraction (hsddp_advance,
+// hsddp_update_problem_measured, hsddp_solve, hsddp_extract_commands_measured); per tick only the B
+// robot states (144 bytes each) go up and the B commands come back.  LCM is not available on this platform: a message
 // is the hkd_data_lcmt struct below and publishing calls a user callback with the
 // hkd_command_lcmt records (hsddp_mpc_command).  The worker serialises updates as mpc_mutex does
 // in the reference (a new request waits for the running update); wait() joins it.
@@ -166,7 +167,10 @@ public:
         }
     }
 
-    // HKDMPCSolver::update (HKDMPC.cpp:96-165)
+    // HKDMPCSolver::update (HKDMPC.cpp:96-165).  The messages' state fields go up as they are
+    // (hsddp_robot_state has hkd_data_lcmt's fields in its order); xinit is formed on the device
+    // from each robot's new first-phase contact, and the extraction reads the foot placements and
+    // the phases' contact durations from the handle: no host model arithmetic, no round trip.
     void update()
     {
         std::lock_guard<std::mutex> lk(mpc_mutex);
@@ -175,42 +179,42 @@ public:
         o.max_DDP_iter = 1;
         chk(hsddp_set_options(h, &o));
         mpc_iter++;
-        // opt_problem.update(): layout, warm start, references; inputs pending until x0 is known
-        std::vector<int> flags(mpc_config.nsteps_between_mpc);
-        chk(hsddp_advance(h, mpc_config.nsteps_between_mpc, mpc_config.plan_duration, dt_mpc, nullptr, flags.data()));
-        int hz[HSDDP_MAX_PHASES];
-        chk(hsddp_get_layout(h, &P, hz, nullptr, nullptr));
-        std::vector<int> contacts((size_t)B * (P + 1) * 4);
-        durations.assign((size_t)B * P * 4, 0.0);
-        chk(hsddp_get_phase_info(h, contacts.data(), durations.data()));
-        // xinit = [eul, pos, omega, vel, qdummy] from the robot state (HKDMPC.cpp:121-134)
-        std::vector<double> x0((size_t)B * 24);
+        robot_states.resize(B);
         for (int b = 0; b < B; ++b) {
             const hkd_data_lcmt &m = hkd_data[b];
-            double *x = &x0[(size_t)b * 24];
+            hsddp_robot_state &r = robot_states[b];
             for (int a = 0; a < 3; ++a) {
-                x[a] = m.rpy[2 - a];
-                x[3 + a] = m.p[a];
-                x[6 + a] = m.omegaBody[a];
-                x[9 + a] = m.vWorld[a];
+                r.p[a] = m.p[a];
+                r.vWorld[a] = m.vWorld[a];
+                r.rpy[a] = m.rpy[a];
+                r.omegaBody[a] = m.omegaBody[a];
             }
-            for (int j = 0; j < 12; ++j) x[12 + j] = m.qJ[j];
+            for (int j = 0; j < 12; ++j) {
+                r.qJ[j] = m.qJ[j];
+                r.foot_placements[j] = m.foot_placements[j];
+            }
         }
-        compute_hkd_state(x0, contacts, P);
-        chk(hsddp_update_problem(h, nullptr, x0.data(), nullptr, nullptr, nullptr));
+        // opt_problem.update(): layout, warm start, references; then xinit = [eul, pos, omega, vel,
+        // qdummy] from the robot states (HKDMPC.cpp:118-134) with the contacts the advance derived
+        std::vector<int> flags(mpc_config.nsteps_between_mpc);
+        chk(hsddp_advance(h, mpc_config.nsteps_between_mpc, mpc_config.plan_duration, dt_mpc, nullptr, flags.data()));
+        chk(hsddp_update_problem_measured(h, nullptr, robot_states.data(), 0, nullptr, nullptr, nullptr));
         const auto t0 = std::chrono::high_resolution_clock::now();
         hsddp_stats st;
         chk(hsddp_solve(h, &st));
         const auto t1 = std::chrono::high_resolution_clock::now();
         solve_time = (float)std::chrono::duration<double, std::milli>(t1 - t0).count();
         // update_foot_placement + publish_mpc_cmd (HKDMPC.cpp:207-298)
-        std::vector<float> pf((size_t)B * 12);
-        for (int b = 0; b < B; ++b)
-            for (int j = 0; j < 12; ++j) pf[(size_t)b * 12 + j] = hkd_data[b].foot_placements[j];
         commands.resize(B);
-        chk(hsddp_extract_commands(h, mpc_config.nsteps_between_mpc, mpc_time, dt_mpc, durations.data(), 1, pf.data(),
-                                   1, solve_time, commands.data()));
+        chk(hsddp_extract_commands_measured(h, mpc_config.nsteps_between_mpc, mpc_time, dt_mpc, nullptr, 0, solve_time,
+                                            commands.data(), 0));
         if (publish) publish(commands);
+        // P and the durations member, for callers that read them: host copies of what the handle
+        // holds, after the commands have left
+        int hz[HSDDP_MAX_PHASES];
+        chk(hsddp_get_layout(h, &P, hz, nullptr, nullptr));
+        durations.assign((size_t)B * P * 4, 0.0);
+        chk(hsddp_get_phase_info(h, nullptr, durations.data()));
     }
 
     // hsddp_simulate_policy for the batch: n_samples states per robot, n_steps knots each (x_init
@@ -274,7 +278,8 @@ public:
     float dt_ref = 0, dt_mpc = 0.01f;
     std::vector<hkd_data_lcmt> hkd_data;
     std::vector<hsddp_mpc_command> commands;
-    std::vector<double> durations;
+    std::vector<double> durations;                 // the phases' contact durations after the last update
+    std::vector<hsddp_robot_state> robot_states;   // the messages' state fields as update() sent them
     bool closed_loop = false;              // the message handler runs update_closed_loop()
     std::vector<hsddp_sim_sample> plant;   // the plant's outcome per robot in the last closed-loop update
     double mpc_time = 0, mpc_time_prev = 0;

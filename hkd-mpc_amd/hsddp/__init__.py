@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from . import model, synthetic  # noqa: F401
-from ._lib import (MPC_COMMAND, PHASE_PLAN, QUAD_STATE, SIM_SAMPLE, ConstraintParams, ElementInfo, HSDDPError, Options, ProblemDesc, Stats, Weights,
+from ._lib import (MPC_COMMAND, PHASE_PLAN, QUAD_STATE, ROBOT_STATE, SIM_SAMPLE, ConstraintParams, ElementInfo, HSDDPError, Options, ProblemDesc, Stats, Weights,
                    check, dp, ip, lib)
 
 SETTINGS_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "settings")
@@ -437,6 +437,42 @@ class Solver:
         check(lib().hsddp_update_problem(self._h, None if contacts is None else ip(self._contacts),
                                          dp(np.ascontiguousarray(x0, dtype=np.float64)),
                                          *(None if r is None else dp(r) for r in refs)))
+
+    def update_problem_measured(self, states=None, contacts=None, ref_x=None, ref_u=None, ref_foot=None,
+                                device_ptr: int | None = None) -> None:
+        """update_problem with x0 formed on the device from the robots' measured states
+        (hsddp_update_problem_measured; HKDMPC.cpp:118-129): states is a [B] ROBOT_STATE array, or
+        device_ptr the address of [B] such records in device memory on the handle's device (e.g. a
+        torch uint8 tensor's data_ptr(); the writes to it complete before the call).  contacts None:
+        the ones advance derived.  The handle keeps the records' foot placements for
+        extract_commands_measured."""
+        self._contacts = None if contacts is None else np.ascontiguousarray(contacts, dtype=np.int32)
+        refs = [None if r is None else np.ascontiguousarray(r, dtype=np.float64) for r in (ref_x, ref_u, ref_foot)]
+        st = None
+        if device_ptr is None and states is not None:
+            st = np.ascontiguousarray(states, dtype=ROBOT_STATE)
+            if st.shape != (self.B,):
+                raise HSDDPError(f"states: shape {st.shape}, expected ({self.B},)")
+        ptr = C.c_void_p(int(device_ptr)) if device_ptr is not None else (None if st is None else st.ctypes.data)
+        check(lib().hsddp_update_problem_measured(self._h, None if contacts is None else ip(self._contacts), ptr,
+                                                  int(device_ptr is not None),
+                                                  *(None if r is None else dp(r) for r in refs)))
+
+    def extract_commands_measured(self, nsteps_between_mpc: int = 1, mpc_time: float = 0.0, dt_mpc: float = 0.01,
+                                  durations=None, solve_time: float = 0.0, out_ptr: int | None = None):
+        """extract_commands with every robot's foot placements taken from the states last given to
+        update_problem_measured (the handle's device copy).  durations: [P, 4] or [B, P, 4]; None: the
+        handle's own phase durations (phase_info's) when the references come from a table, else zeros.
+        out_ptr: [B] hsddp_mpc_command in device memory, as extract_commands_device (returns None);
+        else the [B] record array."""
+        dur = None if durations is None else np.ascontiguousarray(durations, dtype=np.float64)
+        self._check_cmd_inputs(dur, None)
+        out = None if out_ptr is not None else np.zeros(self.B, dtype=MPC_COMMAND)
+        check(lib().hsddp_extract_commands_measured(
+            self._h, int(nsteps_between_mpc), float(mpc_time), float(dt_mpc),
+            None if dur is None else dur.ctypes.data, int(dur is not None and dur.ndim == 3), float(solve_time),
+            C.c_void_p(int(out_ptr)) if out_ptr is not None else out.ctypes.data, int(out_ptr is not None)))
+        return out
 
     def advance(self, x0=None, n_steps: int = 1, plan_duration: float = 0.6, dt_mpc: float = 0.01) -> list:
         """HKDProblem::update from the reference table (hsddp_advance): the window moves n_steps

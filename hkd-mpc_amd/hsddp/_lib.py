@@ -80,6 +80,14 @@ SIM_SAMPLE = np.dtype([("cost", np.float64), ("min_grf", np.float64), ("max_td",
                        ("steps", np.int32), ("status", np.int32)], align=True)
 
 
+# hsddp_robot_state (include/hsddp.h): the state fields of hkd_data_lcmt (lcmtypes/hkd_data_lcmt.lcm),
+# one robot, in the message's order (tests/test_measured_host.py checks size and offsets against the
+# C compiler)
+ROBOT_STATE = np.dtype([("p", np.float32, (3,)), ("vWorld", np.float32, (3,)), ("rpy", np.float32, (3,)),
+                        ("omegaBody", np.float32, (3,)), ("qJ", np.float32, (12,)),
+                        ("foot_placements", np.float32, (12,))], align=True)
+
+
 # hsddp_quad_state (QuadAugmentedState) and hsddp_phase_plan (include/hsddp.h) as C-aligned records
 QUAD_STATE = np.dtype([("body_state", np.float64, (12,)), ("qJ", np.float64, (12,)), ("qJd", np.float64, (12,)),
                        ("foot_placements", np.float64, (12,)), ("grf", np.float64, (12,)),
@@ -116,6 +124,7 @@ EXPORTS = [
     "hsddp_download_constraint_values",
     "hsddp_extract_commands_async", "hsddp_commands_wait",
     "hsddp_simulate_policy", "hsddp_update_problem_simulated",
+    "hsddp_hkd_state", "hsddp_update_problem_measured", "hsddp_extract_commands_measured",
 ]
 
 
@@ -198,6 +207,11 @@ def lib():
     L.hsddp_commands_wait.argtypes = [V, C.c_int, C.POINTER(C.c_void_p)]
     L.hsddp_simulate_policy.argtypes = [V, C.c_int, C.c_int, V, V, V, V, V]
     L.hsddp_update_problem_simulated.argtypes = [V, C.c_int]
+    if hasattr(L, "hsddp_hkd_state"):  # (older A/B builds lack the measured-state ingest)
+        L.hsddp_hkd_state.argtypes = [V, V, V, C.c_int, V]
+        L.hsddp_update_problem_measured.argtypes = [V, IP, V, C.c_int, DP, DP, DP]
+        L.hsddp_extract_commands_measured.argtypes = [V, C.c_int, C.c_double, C.c_double, V, C.c_int, C.c_float, V,
+                                                      C.c_int]
     _lib = L
     return L
 

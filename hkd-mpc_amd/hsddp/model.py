@@ -68,6 +68,19 @@ def foot_position(x, leg):
     return out.get((n, 3))
 
 
+def hkd_state(states, contact):
+    """x0 [n, 24] of HKDMPCSolver::update (HKDMPC.cpp:119-129) from n measured ROBOT_STATE records and
+    each robot's first-phase contact [n, 4]: [eul, pos, omega, vel, qdummy], the qdummy of a stance
+    leg its foot position, of a swing leg its joint angles."""
+    from ._lib import ROBOT_STATE
+    st = np.ascontiguousarray(np.atleast_1d(states), dtype=ROBOT_STATE)
+    n = st.shape[0]
+    ds, dc = _Dev(st.nbytes).put(st), _pts(contact, n, 4, np.int32)
+    out = _Dev(n * 24 * 8)
+    check(lib().hsddp_hkd_state(ds.ptr, dc.ptr, out.ptr, n, None))
+    return out.get((n, 24))
+
+
 def foot_jacobian(x, leg):
     x = np.atleast_2d(x); n = x.shape[0]
     dx, dl = _dev(x), _dev(np.broadcast_to(np.asarray(leg), (n,)), np.int32)

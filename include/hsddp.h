@@ -34,6 +34,11 @@
  *   hsddp_extract_commands(_async)            update_foot_placement + publish_mpc_cmd HKDMPC.cpp:207-298
  *   hsddp_simulate_policy                     SinglePhase::hybrid_rollout's simulated branch at eps = 0 +
  *                                             MultiPhaseDDP::hybrid_rollout's reset  SinglePhase.cpp:196-222; MultiPhaseDDP.cpp:73-81
+ *   hsddp_update_problem_measured             HKDMPCSolver::update's xinit from hkd_data_lcmt (eul, pos, omega,
+ *                                             vel, qdummy) + compute_hkd_state  HKDMPC.cpp:118-129; HKDModel.h:65-96
+ *   hsddp_extract_commands_measured           update_foot_placement + publish_mpc_cmd from the message's
+ *                                             foot_placements and HKDProblemData::contact_durations HKDMPC.cpp:207-298
+ *   hsddp_hkd_state                           compute_hkd_state on the message's fields  HKDModel.h:65-96
  *   hsddp_hkd_dynamics                        HKD::Model::dynamics (hkinodyn)       HKDModel.h:33-45
  *   hsddp_hkd_dynamics_partial                HKD::Model::dynamics_partial          HKDModel.h:46-61
  *   hsddp_hkd_resetmap(_partial)              HKDReset::resetmap(_partial)          HKDReset.h:41-136
@@ -382,7 +387,8 @@ int hsddp_update_problem(hsddp_handle h, const int *contacts, const double *x0, 
  * receives, per step, whether any element saw a contact change.  x0 NULL: the inputs are left
  * pending — read the new first phase's contact (hsddp_get_phase_info), form x0 from it
  * (compute_hkd_state, HKDMPC.cpp:132-134) and call hsddp_update_problem(h, NULL, x0, NULL, NULL,
- * NULL), where NULL contacts are the ones derived here.  The caller's whole MPC tick is
+ * NULL), where NULL contacts are the ones derived here; or hand the robots' measured states to
+ * hsddp_update_problem_measured, which forms x0 on the device.  The caller's whole MPC tick is
  * hsddp_advance + hsddp_solve + hsddp_extract_commands (HKDMPCSolver::update, HKDMPC.cpp:96-165).
  * A phase that would carry more than HSDDP_MAX_TD touchdown constraints keeps its first
  * HSDDP_MAX_TD (the later ones are not registered) and the call returns HSDDP_ERR_UNSUPPORTED after
@@ -398,6 +404,39 @@ int hsddp_advance(hsddp_handle h, int n_steps, float plan_duration, float dt_mpc
 /* The handle's phase bookkeeping: contacts [B][P+1][4] (row P: the last phase's next contact) and,
  * for references built from a table, the phases' contact durations [B][P][4] (either may be NULL). */
 int hsddp_get_phase_info(hsddp_handle h, int *contacts, double *durations);
+
+/* ---- measured robot states: x0 formed on the device ------------------------------------------
+ * The state fields of hkd_data_lcmt (lcmtypes/hkd_data_lcmt.lcm), one robot, in the message's order. */
+typedef struct hsddp_robot_state {
+    float p[3], vWorld[3], rpy[3], omegaBody[3], qJ[12], foot_placements[12];
+} hsddp_robot_state;   /* 144 bytes */
+
+/* hsddp_update_problem with x0 formed on the device from the measured states (HKDMPC.cpp:119-129
+ * with T = double; the float fields widen exactly).  For element b, with c = row 0 of its contacts
+ * in the current layout (with per-element layouts its rows start at b (Pmax + 1)):
+ *     eul = (rpy[2], rpy[1], rpy[0]); pos = p; omega = omegaBody; vel = vWorld
+ *     for l = 0 .. 3: q = qJ[3 l .. 3 l + 2]
+ *         qdummy[3 l .. 3 l + 2] = c[l] == 0 ? q : foot position of leg l at (pos, eul, q)
+ *     x0 = [eul, pos, omega, vel, qdummy]
+ * (the foot position bit for bit hsddp_hkd_foot_position's).  Everything else is
+ * hsddp_update_problem's: the same preconditions and messages, contacts NULL = the ones
+ * hsddp_advance derived, references all three or none, the warm start, working rows, constraint
+ * parameters and stored values kept.  The contacts go to the device first and the kernel runs on the
+ * handle's stream behind that copy.
+ * states_on_device = 0: states [B] is host memory, copied into a device buffer of the handle
+ * (allocated on first use, counted by hsddp_device_bytes, freed by hsddp_destroy; an allocation
+ * that fails returns HSDDP_ERR_ALLOC and leaves the handle usable).  states_on_device = 1: states
+ * [B] is device memory of the handle's device, read in place; the caller's writes must be complete
+ * before the call (nothing is synchronised with other streams), and a pointer the HIP runtime does
+ * not report as device or managed memory of that device, holding B records, is refused with
+ * HSDDP_ERR_ARG before anything is launched.  Any other value, or states NULL: HSDDP_ERR_ARG.
+ * The handle keeps a device copy of the B x 12 foot placements for
+ * hsddp_extract_commands_measured, so the caller's buffer may be released or rewritten once the
+ * call returns.  The copy belongs to this tick: a later hsddp_update_problem, hsddp_upload_problem
+ * or hsddp_update_problem_simulated (an x0 that did not come from a measured record) drops it. */
+int hsddp_update_problem_measured(hsddp_handle h, const int *contacts, const hsddp_robot_state *states,
+                                  int states_on_device, const double *ref_x, const double *ref_u,
+                                  const double *ref_foot);
 
 /* ---- MPC command extraction ------------------------------------------
  * Mirror of hkd_command_lcmt (lcmtypes/hkd_command_lcmt.lcm:1-11), field for field. */
@@ -441,6 +480,15 @@ int hsddp_extract_commands_device(hsddp_handle h, int nsteps_between_mpc, double
                                   const double *status_durations, int durations_per_element,
                                   const float *foot_placements, int feet_per_element, float solve_time,
                                   void *out_device);
+
+/* hsddp_extract_commands (out_on_device = 0: out [B] host array) or hsddp_extract_commands_device
+ * (out_on_device = 1: out [B] on the handle's device) with every element's foot placements taken
+ * from the states last given to hsddp_update_problem_measured (the handle's device copy; none held:
+ * HSDDP_ERR_ARG) and, when status_durations is NULL, the handle's own phase durations — what
+ * hsddp_get_phase_info returns, when the references were built from a table; zeros otherwise. */
+int hsddp_extract_commands_measured(hsddp_handle h, int nsteps_between_mpc, double mpc_time, double dt_mpc,
+                                    const double *status_durations, int durations_per_element,
+                                    float solve_time, hsddp_mpc_command *out, int out_on_device);
 
 /* ---- policy simulation: the plant of the MPC loop, Monte-Carlo evaluation ---------------------
  * The simulated branch of SinglePhase::hybrid_rollout at eps = 0 (SinglePhase.cpp:196-222) with
@@ -504,6 +552,8 @@ int hsddp_hkd_dynamics_partial(const double *x, const double *u, const double *c
                                double *A, double *B, int n, void *stream);
 /* p[n][3] = compute_foot_position(pos, eul, qleg, leg+1) with q = x[12+3leg..], pos = x[3..5], eul = x[0..2]; leg[n] */
 int hsddp_hkd_foot_position(const double *x, const int *leg, double *p, int n, void *stream);
+/* x[n][24] = the initial state of hsddp_update_problem_measured from states[n] and contact int32 [n][4] */
+int hsddp_hkd_state(const hsddp_robot_state *states, const int *contact, double *x, int n, void *stream);
 /* J[n][3*18] column-major, columns [pos(3) | eul(3) | qJ(12)] as comp_foot_jacob_{leg+1} */
 int hsddp_hkd_foot_jacobian(const double *x, const int *leg, double *J, int n, void *stream);
 /* c, cn int32 [n][4] */

@@ -12,6 +12,13 @@ wall-clock split is per stage; kernel durations come from rocprofv3 over the sam
 tick's step (hsddp_simulate_policy, one sample per robot), handed over by
 hsddp_update_problem_simulated after an advance with pending inputs; the plant's time per tick
 is reported beside advance (which then includes that hand-over) and solve.
+
+--host-state and --measured feed both the same measured robot records (hsddp_robot_state, seeded)
+tick by tick and time the two ways from a record to the handle's x0: --host-state is the caller's
+route without the ingest (advance with pending inputs, phase_info's contacts, the foot-position
+primitive on 4 B replicated rows, update_problem(None, x0)); --measured is advance +
+update_problem_measured, with the commands from extract_commands_measured.  "advance" is then the
+whole of it, "state" the part after hsddp_advance.
 """
 import argparse
 import json
@@ -27,6 +34,18 @@ sys.path.insert(0, os.path.join(ROOT, "hkd-mpc_amd"))
 import hsddp  # noqa: E402
 
 
+def robot_records(rng, B):
+    """[B] measured states near the nominal stance (hsddp_robot_state, all float32)"""
+    r = np.zeros(B, dtype=hsddp.ROBOT_STATE)
+    r["p"] = np.array([0.0, 0.0, 0.25]) + rng.uniform(-1, 1, (B, 3)) * np.array([0.01, 0.01, 0.005])
+    r["rpy"] = rng.uniform(-.02, .02, (B, 3))
+    r["omegaBody"] = rng.uniform(-.1, .1, (B, 3))
+    r["vWorld"] = rng.uniform(-.1, .1, (B, 3))
+    r["qJ"] = np.tile([0.0, -0.8, 1.6], 4) + rng.uniform(-.02, .02, (B, 12))
+    r["foot_placements"] = np.float32([.2, -.14, 0, .2, .14, 0, -.2, -.14, 0, -.2, .14, 0])
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096)
@@ -36,7 +55,13 @@ def main():
                          "asynchronous copy into the handle's pinned buffers")
     ap.add_argument("--closed-loop", action="store_true",
                     help="x0 of every tick from the policy simulated on the device instead of host noise")
+    ap.add_argument("--host-state", action="store_true",
+                    help="x0 of every tick formed on the host from measured records (the route without the ingest)")
+    ap.add_argument("--measured", action="store_true",
+                    help="x0 of every tick formed on the device from the same records (update_problem_measured)")
     args = ap.parse_args()
+    if args.host_state + args.measured + args.closed_loop > 1:
+        ap.error("--host-state, --measured and --closed-loop are separate legs")
     B = args.batch
     tab, dt = hsddp.load_quad_reference(os.path.join(ROOT, "tests", "golden", "ref_trot.csv"))
     rng = np.random.default_rng(7)
@@ -49,7 +74,8 @@ def main():
     s.solve()
     s.set_options(hsddp.load_settings(max_AL_iter=2, max_DDP_iter=1))
     feet = np.tile(np.float32([.2, -.14, 0, .2, .14, 0, -.2, -.14, 0, -.2, .14, 0]), (B, 1))
-    t_adv, t_solve, t_cmd, t_plant = [], [], [], []
+    t_adv, t_solve, t_cmd, t_plant, t_state = [], [], [], [], []
+    legs = np.tile(np.arange(4, dtype=np.int32), B)
     plant_ok = True
     flags = 0
     ticket, cmd, t_last = None, None, 0.0
@@ -62,6 +88,24 @@ def main():
             plant_ok = plant_ok and bool(np.all(plant["summary"]["status"] == 0))
             flags += sum(s.advance(None, 1))
             s.update_problem_simulated(0)
+        elif args.host_state or args.measured:
+            rec = robot_records(rng, B)
+            feet = rec["foot_placements"]
+            t0 = time.perf_counter()
+            flags += sum(s.advance(None, 1))
+            ts = time.perf_counter()
+            if args.measured:
+                s.update_problem_measured(rec)
+            else:  # compute_hkd_state by hand: every robot's row once per leg through the primitive
+                c0 = s.phase_info()["contacts"][:, 0]
+                xt = np.zeros((B, 24))
+                xt[:, 0:3], xt[:, 3:6] = rec["rpy"][:, ::-1], rec["p"]
+                xt[:, 6:9], xt[:, 9:12], xt[:, 12:] = rec["omegaBody"], rec["vWorld"], rec["qJ"]
+                fp = hsddp.model.foot_position(np.repeat(xt, 4, axis=0), legs).reshape(B, 12)
+                on = np.repeat(c0 != 0, 3, axis=1)
+                xt[:, 12:][on] = fp[on]
+                s.update_problem(None, xt)
+            t_state.append(time.perf_counter() - ts)
         else:
             xt = x0 + rng.uniform(-.01, .01, x0.shape)
             t0 = time.perf_counter()
@@ -69,9 +113,11 @@ def main():
         t1 = time.perf_counter()
         s.solve()
         t2 = time.perf_counter()
-        info = s.phase_info()
+        info = None if args.measured else s.phase_info()
         t3 = time.perf_counter()
-        if args.sync:
+        if args.measured:  # feet and durations from the handle
+            cmd = s.extract_commands_measured(1, 0.01 * (it + 1), float(np.float32(0.01)), None, 0.0)
+        elif args.sync:
             cmd = s.extract_commands(1, 0.01 * (it + 1), float(np.float32(0.01)), info["durations"], feet, 0.0)
         else:  # the records of tick t cross PCIe during tick t + 1's advance and solve
             if ticket is not None:
@@ -80,7 +126,7 @@ def main():
                                               0.0)
         t4 = time.perf_counter()
         t_adv.append(t1 - t0); t_solve.append(t2 - t1); t_cmd.append(t4 - t3)
-    if not args.sync:
+    if not args.sync and not args.measured:
         t5 = time.perf_counter()
         cmd = s.commands_wait(ticket, copy=False)
         t_last = time.perf_counter() - t5
@@ -94,7 +140,7 @@ def main():
     out = {"metric": "MPC tick (advance + solve + extract), HKD trot reference file", "batch": B,
            "ticks": args.ticks, "plan_knots": Kc, "final_horizons": lay["horizons"], "contact_change_steps": flags,
            "ms_per_tick_median": {"advance": med(t_adv), "solve": med(t_solve), "extract_commands": med(t_cmd)},
-           "extract_mode": "sync (pageable)" if args.sync else "async (pinned, overlapped with the next tick)",
+           "extract_mode": "sync (pageable)" if args.sync or args.measured else "async (pinned, overlapped with the next tick)",
            "last_copy_wait_ms": t_last * 1e3,
            "robot_ticks_per_s": B / (np.median(t_adv) + np.median(t_solve) + np.median(t_cmd)),
            "shift_gather_algorithmic_bytes": shift_bytes, "all_finite": finite}
@@ -102,6 +148,10 @@ def main():
         out["metric"] = "closed-loop MPC tick (plant + advance + solve + extract), HKD trot reference file"
         out["ms_per_tick_median"]["plant"] = med(t_plant)
         out["plant_all_ok"] = plant_ok
+    if args.host_state or args.measured:
+        out["metric"] = ("MPC tick from measured robot states, x0 formed on the %s, HKD trot reference file"
+                         % ("device (update_problem_measured)" if args.measured else "host (foot-position primitive)"))
+        out["ms_per_tick_median"]["state"] = med(t_state)
     print(json.dumps(out), flush=True)
     s.close()
 
