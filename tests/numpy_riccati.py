@@ -16,12 +16,21 @@ MU = 0.7
 MASS_G = 8.912 * 9.81
 
 
-def weights(c):
-    q = np.array([1, 4, 5, 1, 1, 30, .2, .2, .2, 4, 1, .5] + [.2 * (1 - c[l]) for l in range(4) for _ in range(3)])
-    sc = np.array([1, 1, 2, 1, 1, 20, .3, .3, .3, 1, 3, 1] + [.01] * 12)
-    Qf = 20 * sc * q
-    R = np.array([.2] * 12 + [.1] * 12)
-    W = np.array([20 * w * c[l] for l in range(4) for w in (3, 1, 0)])
+# the HKD cost weights (HKDCost.h:111-166, HKDCost.cpp:49,63-64) by the oracle's field names
+DEFAULT_W = {"q_eul": (1, 4, 5), "q_pos": (1, 1, 30), "q_omega": (.2, .2, .2), "q_v": (4, 1, .5), "q_qJ": .2,
+             "qf_scale": (1, 1, 2, 1, 1, 20, .3, .3, .3, 1, 3, 1) + (.01,) * 12, "qf_gain": 20, "r_grf": .2,
+             "r_qJd": .1, "foot_w": (3, 1, 0), "foot_gain": 20, "foot_term_cost": 10, "foot_term_grad": 20}
+
+
+def weights(c, w=None):
+    """Q, Qf, R, W (diagonal) and D = dprel_dx of a phase with contact c; w: overrides of DEFAULT_W."""
+    w = {**DEFAULT_W, **(w or {})}
+    q = np.array(list(w["q_eul"]) + list(w["q_pos"]) + list(w["q_omega"]) + list(w["q_v"])
+                 + [w["q_qJ"] * (1 - c[l]) for l in range(4) for _ in range(3)], dtype=float)
+    sc = np.array(w["qf_scale"], dtype=float)
+    Qf = w["qf_gain"] * sc * q
+    R = np.array([w["r_grf"]] * 12 + [w["r_qJd"]] * 12, dtype=float)
+    W = np.array([w["foot_gain"] * fw * c[l] for l in range(4) for fw in w["foot_w"]], dtype=float)
     D = np.zeros((12, 24))
     for l in range(4):
         D[3 * l:3 * l + 3, 3:6] = -c[l] * np.eye(3)
@@ -29,16 +38,17 @@ def weights(c):
     return np.diag(q), np.diag(Qf), np.diag(R), np.diag(W), D
 
 
-def grf_A(c):
+def grf_A(c, mu=MU):
     rows = []
     for l in range(4):
         if c[l]:
-            for r in ([0, 0, 1], [-1, 0, MU], [1, 0, MU], [0, -1, MU], [0, 1, MU]):
+            for r in ([0, 0, 1], [-1, 0, mu], [1, 0, mu], [0, -1, mu], [0, 1, mu]):
                 a = np.zeros(24); a[3 * l:3 * l + 3] = r; rows.append(a)
     return np.array(rows).reshape(-1, 24)
 
 
-def foot_height_grad(x, l):
+def foot_height_grad(x, l, ground=0.0):
+    """Touchdown residual h = foot height - ground (HKDConstraints.cpp:69-118) and its gradient."""
     J = np.zeros(54)
     O.lib().orc_foot_jacobian(l, O.dp(np.ascontiguousarray(x[3:6])), O.dp(np.ascontiguousarray(x[0:3])),
                               O.dp(np.ascontiguousarray(x[12 + 3 * l:15 + 3 * l])), O.dp(J))
@@ -47,11 +57,13 @@ def foot_height_grad(x, l):
     O.lib().orc_foot_position(l, O.dp(np.ascontiguousarray(x[3:6])), O.dp(np.ascontiguousarray(x[0:3])),
                               O.dp(np.ascontiguousarray(x[12 + 3 * l:15 + 3 * l])), O.dp(p))
     hx = np.zeros(24); hx[0:3] = J[2, 3:6]; hx[3:6] = J[2, 0:3]; hx[12:24] = J[2, 6:18]
-    return p[2], hx
+    return p[2] - ground, hx
 
 
-def sweep(prob, b, X, U, Defect, reg=0.0, delta=0.1, eps=0.1, sigma=50.0, lam=0.0):
-    """One backward sweep + linear rollout at (X, U, Defect) for element b.  Returns dict."""
+def sweep(prob, b, X, U, Defect, reg=0.0, delta=0.1, eps=0.1, sigma=50.0, lam=0.0, w=None, mu=MU, ground=0.0):
+    """One backward sweep + linear rollout at (X, U, Defect) for element b.  Returns dict.
+    w: cost-weight overrides (DEFAULT_W's keys); mu: friction coefficient; ground: ground height."""
+    ftg = {**DEFAULT_W, **(w or {})}["foot_term_grad"]
     hz = prob["horizons"]; dt = prob["dt"]; P = len(hz)
     cont = prob["contacts"][b]
     rb = 0 if prob["ref_x"].shape[0] == 1 else b
@@ -60,8 +72,8 @@ def sweep(prob, b, X, U, Defect, reg=0.0, delta=0.1, eps=0.1, sigma=50.0, lam=0.
     lq = []
     for i in range(P):
         c = cont[i]; cn = cont[i + 1]
-        Q, Qf, R, W, D = weights(c)
-        Ag = grf_A(c)
+        Q, Qf, R, W, D = weights(c, w)
+        Ag = grf_A(c, mu)
         ks = []
         for k in range(hz[i]):
             s, kc = s0[i] + k, k0[i] + k
@@ -84,11 +96,11 @@ def sweep(prob, b, X, U, Defect, reg=0.0, delta=0.1, eps=0.1, sigma=50.0, lam=0.
         s = s0[i] + hz[i]; x = X[s]
         dx = x - xr_all[s]
         d = (x[12:] - np.tile(x[3:6], 4)) - (pf_all[s] - np.tile(xr_all[s, 3:6], 4))
-        Phix = Qf @ dx + 20 * D.T @ W @ d
-        Phixx = Qf + 20 * D.T @ W @ D
+        Phix = Qf @ dx + ftg * D.T @ W @ d
+        Phixx = Qf + ftg * D.T @ W @ D
         for l in range(4):
             if c[l] == 0 and cn[l] == 1:
-                h, hx = foot_height_grad(x, l)
+                h, hx = foot_height_grad(x, l, ground)
                 Phix = Phix + (sigma * h + lam) * hx
                 Phixx = Phixx + (sigma * (1 + h) + lam) * np.outer(hx, hx)
         Px = O.resetmap_partial(x, c, cn) if i < P - 1 else None

@@ -121,7 +121,26 @@ def default_options(**kw) -> OrcOptions:
     return o
 
 
-def default_problem(horizons, dt=0.01) -> tuple:
+CPARAM_FIELDS = ("mu_fric", "grf_delta", "grf_delta_min", "grf_eps", "td_sigma", "td_sigma_max", "td_lambda",
+                 "ground_height")
+
+
+def set_weights(w: OrcWeights, weights: dict | None) -> None:
+    """Cost-weight overrides by field name; the array fields (q_eul ... foot_w: 3, qf_scale: 24) take
+    any sequence of that length."""
+    for k, v in (weights or {}).items():
+        cur = getattr(w, k)
+        if isinstance(cur, C.Array):
+            v = [float(a) for a in v]
+            if len(v) != len(cur):
+                raise ValueError(f"weights[{k!r}]: {len(v)} values, expected {len(cur)}")
+            v = type(cur)(*v)
+        setattr(w, k, v)
+
+
+def default_problem(horizons, dt=0.01, cparams: dict | None = None) -> tuple:
+    """cparams: overrides of OrcProblem's mu_fric ... ground_height (CPARAM_FIELDS), applied after
+    the defaults."""
     hz = np.asarray(horizons, dtype=np.int32)
     p = OrcProblem()
     p.n_phases = len(hz)
@@ -132,6 +151,10 @@ def default_problem(horizons, dt=0.01) -> tuple:
     p.td_sigma, p.td_sigma_max, p.td_lambda = 50.0, 1e4, 0.0
     p.ground_height = 0.0
     lib().orc_default_weights(C.byref(p.w))
+    for k, v in (cparams or {}).items():
+        if k not in CPARAM_FIELDS:
+            raise KeyError(f"cparams[{k!r}]: not one of {CPARAM_FIELDS}")
+        setattr(p, k, float(v))
     return p, hz
 
 
@@ -165,11 +188,10 @@ def resetmap_partial(x, c, cn):
 
 
 def knot_eval(c, cn, x, u, xr, ur, pf, x_end=None, xr_end=None, pf_end=None, reb_delta=None, reb_eps=None,
-              sigma=None, lam=None, options=None, dt=0.01, weights=None) -> dict:
+              sigma=None, lam=None, options=None, dt=0.01, weights=None, cparams=None) -> dict:
     """orc_knot_eval: one knot's cost and LQ model, and one phase end's terminal data, alone."""
-    p, _hz = default_problem([1], dt)
-    for k, v in (weights or {}).items():
-        setattr(p.w, k, v)
+    p, _hz = default_problem([1], dt, cparams)
+    set_weights(p.w, weights)
     o = options or default_options()
     f = lambda a, n: np.ascontiguousarray(np.zeros(n) if a is None else a, dtype=np.float64)
     args = [f(x, 24), f(u, 24), f(xr, 24), f(ur, 24), f(pf, 12), f(x if x_end is None else x_end, 24),
@@ -216,9 +238,10 @@ STEP_FIELDS = ("dX", "dU")
 
 def solve_batch(prob: dict, options: OrcOptions | None = None, n_threads: int = 1,
                 elements=None, weights: dict | None = None, constraints: dict | None = None,
-                state: dict | None = None) -> dict:
+                state: dict | None = None, cparams: dict | None = None) -> dict:
     """Run the oracle solve on (a subset of) a synthetic batch; returns per-element outputs.
     weights: HKD cost-weight overrides by field name (e.g. {"r_qJd": -0.5}).
+    cparams: constraint-parameter overrides (CPARAM_FIELDS, e.g. {"mu_fric": 0.4}).
     constraints: the elements' constraint parameters (CONSTRAINT_FIELDS, [B] leading axis) to start
     from instead of a new problem's (orc_init_element) — an MPC tick's carried-over ReB / AL
     parameters and touchdown constraints; the outputs carry them after the solve.
@@ -230,9 +253,8 @@ def solve_batch(prob: dict, options: OrcOptions | None = None, n_threads: int = 
     idx = list(range(B)) if elements is None else list(elements)
     n = len(idx)
     S, Kc, P = prob["S"], prob["Kc"], len(prob["horizons"])
-    p, hz = default_problem(prob["horizons"], prob["dt"])
-    for k, v in (weights or {}).items():
-        setattr(p.w, k, v)
+    p, hz = default_problem(prob["horizons"], prob["dt"], cparams)
+    set_weights(p.w, weights)
     ss = None
     if prob.get("shooting") is not None:  # shooting states per phase (after a receding-horizon shift)
         ss = np.ascontiguousarray(prob["shooting"], dtype=np.int32)

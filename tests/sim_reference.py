@@ -36,8 +36,9 @@ def element_layouts(prob):
     return [list(h) for h in (prob.get("layouts") or [prob["horizons"]] * prob["batch"])]
 
 
-def simulate(prob, traj, x_init, n_steps, mu=MU_FRIC, ground=GROUND_HEIGHT):
-    """prob: horizons / layouts, contacts [B][Pmax+1][4], dt, ref_x, ref_u [Bref][S][24], ref_foot
+def simulate(prob, traj, x_init, n_steps, mu=MU_FRIC, ground=GROUND_HEIGHT, weights=None):
+    """weights: cost-weight overrides by field name (O.knot_eval's); mu, ground: the handle's
+    mu_fric and ground_height.  prob: horizons / layouts, contacts [B][Pmax+1][4], dt, ref_x, ref_u [Bref][S][24], ref_foot
     [Bref][S][12]; traj: Xbar [B][S][24], Ubar [B][Kc][24], K [B][Kc][24][24]; x_init [B][M][24].
     Returns X, U [B][M][n][24] (zero past a diverged sample's break knot), after [B][M][n][24] (the
     state after knot j, through the reset map at a phase end with a successor), the running totals
@@ -78,7 +79,7 @@ def simulate(prob, traj, x_init, n_steps, mu=MU_FRIC, ground=GROUND_HEIGHT):
                 if not ok:  # (a NaN compares false: diverged)
                     out["status"][b, m] = 1
                     break
-                ev = O.knot_eval(c, cn, x, u, rx[s], ru[s], rf[s], options=opt, dt=dt)
+                ev = O.knot_eval(c, cn, x, u, rx[s], ru[s], rf[s], options=opt, dt=dt, weights=weights)
                 cost += ev["l"]
                 for leg in range(4):
                     if c[leg]:
@@ -87,7 +88,7 @@ def simulate(prob, traj, x_init, n_steps, mu=MU_FRIC, ground=GROUND_HEIGHT):
                 x = xs
                 if k == hz[i] - 1:
                     ev = O.knot_eval(c, cn, x, np.zeros(24), rx[s + 1], ru[s + 1], rf[s + 1], x_end=x, xr_end=rx[s + 1],
-                                     pf_end=rf[s + 1], options=opt, dt=dt)
+                                     pf_end=rf[s + 1], options=opt, dt=dt, weights=weights)
                     cost += ev["Phi"]
                     for leg in range(4):
                         if c[leg] == 0 and cn[leg] == 1:

@@ -130,23 +130,30 @@ def test_shift_matches_oracle(steps):
     s.close()
 
 
-@pytest.mark.parametrize("ms", [1, 0])
-def test_mpc_loop_matches_oracle(ms):
+@pytest.mark.parametrize("ms,params", [(1, False), (0, False), (1, True)], ids=["1", "0", "1-parameters"])
+def test_mpc_loop_matches_oracle(ms, params):
     """HKDMPCSolver::update's loop (HKDMPC.cpp:96-165): shift one step, new inputs with the warm
     start kept, re-solve with max_AL_iter = 2, max_DDP_iter = 1 (quirk A17) — including the
     updates whose new last phase has no shooting states — against the oracle doing the same; with
-    multiple (MS 1) and single (MS 0) shooting."""
+    multiple (MS 1) and single (MS 0) shooting.  The "parameters" variant runs on
+    solver_params.CPARAMS with the ReB / AL schedule on (update_ReB 7, update_relax 0.1,
+    update_penalty 3): pushed-back knots and newly registered touchdown constraints start from
+    non-default initial parameters while the shifted ones carry moved values."""
+    import solver_params as SP
     B, P, N = 8, 4, 5
     sc, prob = _scenario_batch(B, P, N)
-    s = hsddp.Solver(prob, hsddp.load_settings(MS=ms))
+    sched = dict(SP.SCHEDULE) if params else {}
+    cpd = SP.CPARAMS if params else None
+    s = hsddp.Solver(prob, hsddp.load_settings(MS=ms, **sched), cparams=SP.hsddp_cparams() if params else None)
     s.solve()
-    r = O.solve_batch(prob, O.default_options(MS=ms), n_threads=8)
+    r = O.solve_batch(prob, O.default_options(MS=ms, **sched), n_threads=8, cparams=cpd)
     g = {**s.trajectory(), **s.working(), **s.element_info()}
     assert _rel(g["Xbar"], r["Xbar"]) < 1e-9
-    kw = dict(max_AL_iter=2, max_DDP_iter=1, MS=ms)
+    kw = dict(max_AL_iter=2, max_DDP_iter=1, MS=ms, **sched)
     s.set_options(hsddp.load_settings(**kw))
     tails = n_td = 0
-    op, _ = O.default_problem(prob["horizons"], prob["dt"])  # the initial ReB / AL parameters
+    op, _ = O.default_problem(prob["horizons"], prob["dt"], cpd)  # the initial ReB / AL parameters
+    moved = lam_moved = 0
     for it in range(9):
         lay0 = s.layout()
         flags = sc.step(1)
@@ -169,7 +176,11 @@ def test_mpc_loop_matches_oracle(ms):
               "S": sum(n + 1 for n in lay["horizons"]), "Kc": sum(lay["horizons"]), **inp,
               "Xbar": np.stack([q[3] for q in sh]), "Ubar": np.stack([q[4] for q in sh]),
               "K": np.stack([q[5] for q in sh])}
-        r = O.solve_batch(p2, O.default_options(**kw), n_threads=8, constraints=cons)
+        r = O.solve_batch(p2, O.default_options(**kw), n_threads=8, constraints=cons, cparams=cpd)
+        # carried-over rows that differ from the initial values meet new rows that hold them
+        moved += bool(np.any(cons["reb_eps"] != op.grf_eps) and np.any(cons["reb_eps"] == op.grf_eps)
+                      and np.any(cons["al_sigma"] != op.td_sigma))
+        lam_moved += params and SP.lambda_moved(r, SP.CPARAMS)  # a multiplier update from td_lambda = 0.3
         dc = s.constraint_params()
         assert np.array_equal(dc["td_mask"], r["td_mask"]), it
         n_td = max(n_td, int((dc["td_mask"] != 0).sum(axis=2).max()))
@@ -181,6 +192,7 @@ def test_mpc_loop_matches_oracle(ms):
         assert _rel(g["cost"], r["cost"]) < 1e-9, it
     assert tails >= 2  # the loop passed through last phases without shooting states
     assert n_td >= 1   # (phases carrying two touchdown constraints: test_gpu_reference.py's file-driven loop)
+    assert (moved >= 1 and lam_moved >= 1) or not params
     s.close()
 
 

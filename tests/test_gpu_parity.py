@@ -345,6 +345,44 @@ def test_trajectory_exports_match_numpy_restatement(gait, P, N):
             assert abs(total - info["cost"][b]) <= 1e-12 * abs(total), b
 
 
+@pytest.mark.parametrize("gait,P,N", [("trot", 2, 8), ("jump", 8, 4)])
+def test_trajectory_exports_at_nondefault_parameters(gait, P, N):
+    """The same exports at solver_params.WEIGHTS / CPARAMS (grf_eps = 0.3) from warm-start controls
+    with friction-pyramid rows on both sides of delta: the log branch of the barrier, non-zero z
+    foot-placement terms, td_lambda != 0 and ground_height != 0 in the exported records."""
+    import solver_params as SP
+    from test_oracle_parameters import assert_both_branches, numpy_sweep, sweep_problem
+    B = 3
+    prob, cp = sweep_problem(gait, P, N, 0.01)
+    assert_both_branches(prob, cp)
+    s = hsddp.Solver(prob, hsddp.load_settings(no_early_exit=1, max_AL_iter=1, max_DDP_iter=1),
+                     cparams=SP.hsddp_cparams(cp), weights=SP.hsddp_weights())
+    s.set_value_export(True)
+    s.solve()
+    lq, tm, v, info = s.lq(), s.terminal(), s.value(), s.element_info()
+    s.close()
+    k0 = np.cumsum([0] + list(prob["horizons"]))
+    for b in range(B):
+        ref = numpy_sweep(prob, b, cp, SP.WEIGHTS)
+        for i in range(P):
+            ks, Phix, Phixx, Px = ref["lq"][i]
+            for k in range(prob["horizons"][i]):
+                kc = k0[i] + k
+                for name, want in zip(("A", "B", "lx", "lu", "lxx", "luu"), ks[k]):
+                    assert rel(lq[name][b, kc], want) < 1e-12, (b, kc, name)
+            assert rel(tm["Phix"][b, i], Phix) < 1e-12, (b, i)
+            assert rel(tm["Phixx"][b, i], Phixx) < 1e-12, (b, i)
+            if Px is None:
+                assert np.all(tm["Px"][b, i] == 0)
+            else:
+                assert rel(tm["Px"][b, i], Px) < 1e-12, (b, i)
+        assert rel(v["G"][b], ref["G0"]) < 1e-9, b
+        assert rel(v["H"][b], ref["H0"]) < 1e-9, b
+        if info["n_ls_trials"][b] < 4:  # accepted: the last trial's slot costs are the element's cost
+            total = lq["l"][b].sum() + tm["Phi"][b].sum()
+            assert abs(total - info["cost"][b]) <= 1e-12 * abs(total), b
+
+
 def test_failed_line_search_keeps_the_last_trial():
     """Quirk A2 (MultiPhaseDDP.cpp:345-353) on the device: gamma = 1e6 rejects every trial, so the
     nominal rows stay and the working rows are the last trial (eps = 0.001) — the buffer-flip

@@ -11,6 +11,7 @@ import pytest
 
 import hsddp
 import oracle_lib as O
+import solver_params as SP
 from hsddp import model
 from test_oracle_pinning import CASES, _control, _refs, _state, _height_and_grad
 
@@ -22,21 +23,28 @@ def _close(a, b, tol=1e-12):
     return np.max(np.abs(a - b)) <= tol * max(1.0, np.max(np.abs(b)))
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("c,cn,seed", CASES)
-def test_running_plugins_sum_to_the_oracle_knot(c, cn, seed):
+# the second variant of every plugin test: solver_params.WEIGHTS, mu = 0.4, ground = 0.02, dt = 0.02
+NONDEFAULT = dict(weights=SP.WEIGHTS, cparams=SP.CPARAMS, DT=0.02)
+
+
+def _running_plugins_sum_to_the_oracle_knot(c, cn, seed, weights=None, cparams=None, DT=DT):
     x, u = _state(c, seed), _control(c, seed)
     xr, ur, pf = _refs(c)
-    r = O.knot_eval(c, cn, x, u, xr, ur, pf)
-    rc = {k: v[0] for k, v in model.running_cost(x, u, c, xr, ur, pf).items()}
-    track = {k: v[0] for k, v in model.running_cost(x, u, c, xr, ur, pf, terms=model.TERM_TRACKING).items()}
-    foot = {k: v[0] for k, v in model.running_cost(x, u, c, xr, ur, pf, terms=model.TERM_FOOT).items()}
+    r = O.knot_eval(c, cn, x, u, xr, ur, pf, weights=weights, cparams=cparams, dt=DT)
+    kw = dict(dt=DT, weights=None if weights is None else SP.hsddp_weights(weights))
+    rc = {k: v[0] for k, v in model.running_cost(x, u, c, xr, ur, pf, **kw).items()}
+    track = {k: v[0] for k, v in model.running_cost(x, u, c, xr, ur, pf, terms=model.TERM_TRACKING, **kw).items()}
+    foot = {k: v[0] for k, v in model.running_cost(x, u, c, xr, ur, pf, terms=model.TERM_FOOT, **kw).items()}
     for k in ("lx", "lu", "lxx", "luu"):   # the terms are additive (RCostData::add)
         assert _close(track[k] + foot[k], rc[k], 1e-15), k
-    g, gu = model.grf_constraint(u, c)
     n = 5 * int(sum(c))
-    cp = hsddp.load_constraint_params()
-    delta, eps = cp.grf_delta, cp.grf_eps
+    if cparams is None:
+        g, gu = model.grf_constraint(u, c)
+        cp = hsddp.load_constraint_params()
+        delta, eps = cp.grf_delta, cp.grf_eps
+    else:
+        g, gu = model.grf_constraint(u, c, mu=cparams["mu_fric"])
+        delta, eps = cparams["grf_delta"], cparams["grf_eps"]
     barr = bd = 0.0
     lu, luu = rc["lu"].copy(), rc["luu"].copy()
     rb = 0.0
@@ -58,22 +66,57 @@ def test_running_plugins_sum_to_the_oracle_knot(c, cn, seed):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("c,seed", [((1, 0, 0, 1), 5), ((1, 1, 1, 1), 6), ((0, 0, 0, 0), 7)])
-def test_terminal_plugins_match_the_oracle(c, seed):
+@pytest.mark.parametrize("c,cn,seed", CASES)
+def test_running_plugins_sum_to_the_oracle_knot(c, cn, seed):
+    _running_plugins_sum_to_the_oracle_knot(c, cn, seed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c,cn,seed", CASES)
+def test_running_plugins_sum_to_the_oracle_knot_at_nondefault_parameters(c, cn, seed):
+    _running_plugins_sum_to_the_oracle_knot(c, cn, seed, **NONDEFAULT)
+
+
+def _terminal_plugins_match_the_oracle(c, seed, weights=None):
     x = _state(c, seed)
     xr, ur, pf = _refs(c)
-    r = O.knot_eval(c, c, x, np.zeros(24), xr, ur, pf, x_end=x)   # no touchdown: no AL terms
-    t = {k: v[0] for k, v in model.terminal_cost(x, c, xr, pf).items()}
+    r = O.knot_eval(c, c, x, np.zeros(24), xr, ur, pf, x_end=x, weights=weights)   # no touchdown: no AL terms
+    w = None if weights is None else SP.hsddp_weights(weights)
+    t = {k: v[0] for k, v in model.terminal_cost(x, c, xr, pf, weights=w).items()}
     assert _close(t["Phi"], r["Phi"], 1e-13)
     assert _close(t["Phix"], r["Phix"]) and _close(t["Phixx"], r["Phixx"])
 
 
+TERMINAL_CASES = [((1, 0, 0, 1), 5), ((1, 1, 1, 1), 6), ((0, 0, 0, 0), 7)]
+
+
 @pytest.mark.gpu
-def test_touchdown_plugin_matches_foot_kinematics():
+@pytest.mark.parametrize("c,seed", TERMINAL_CASES)
+def test_terminal_plugins_match_the_oracle(c, seed):
+    _terminal_plugins_match_the_oracle(c, seed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c,seed", TERMINAL_CASES)
+def test_terminal_plugins_match_the_oracle_at_nondefault_weights(c, seed):
+    _terminal_plugins_match_the_oracle(c, seed, SP.WEIGHTS)
+
+
+def _touchdown_plugin_matches_foot_kinematics(ground):
     c, cn = (1, 0, 0, 1), (1, 1, 1, 1)    # legs 1 and 2 touch down
     x = _state(c, 11)
-    h, hx = model.touchdown_constraint(x, c, cn, ground=0.0)
+    h, hx = model.touchdown_constraint(x, c, cn, ground=ground)
     for row, leg in enumerate((1, 2)):
         hr, hxr = _height_and_grad(x, leg)
-        assert _close(h[0, row], hr, 1e-13) and _close(hx[0, row], hxr, 1e-13)
+        assert _close(h[0, row], hr - ground, 1e-13) and _close(hx[0, row], hxr, 1e-13)
     assert np.all(h[0, 2:] == 0) and np.all(hx[0, 2:] == 0)
+
+
+@pytest.mark.gpu
+def test_touchdown_plugin_matches_foot_kinematics():
+    _touchdown_plugin_matches_foot_kinematics(0.0)
+
+
+@pytest.mark.gpu
+def test_touchdown_plugin_matches_foot_kinematics_above_the_ground():
+    _touchdown_plugin_matches_foot_kinematics(SP.CPARAMS["ground_height"])

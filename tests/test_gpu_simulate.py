@@ -139,6 +139,24 @@ def test_fp32_handle_matches_helper():
     check(g, ref, ref2, 12, "fp32")
 
 
+# ---- 3b. a handle with its own weights and constraint parameters ---------------------------------
+def test_nondefault_parameters_match_helper():
+    """solver_params.WEIGHTS / CPARAMS: the running and terminal costs by these weights (z foot terms
+    included), min_grf by mu = 0.4, max_td against ground = 0.02."""
+    import solver_params as SP
+    prob = syn.make_batch(3, 3, 4, "trot")
+    s, tr = solved(prob, weights=SP.hsddp_weights(), cparams=SP.hsddp_cparams())
+    x = perturbed(tr["Xbar"][:, 0], 5, seed=25)
+    kw = dict(mu=SP.CPARAMS["mu_fric"], ground=SP.CPARAMS["ground_height"], weights=SP.WEIGHTS)
+    ref = R.simulate(prob, tr, x, 12, **kw)
+    ref2 = R.simulate(prob, tr, x * (1 + 1e-15), 12, **kw)
+    assert np.all(ref["status"] == 0)
+    for n in (4, 12):  # a phase end (the touchdown heights enter max_td), the whole horizon
+        g = flat(s.simulate_policy(x, n, trajectories=True))
+        check(g, ref, ref2, n, "parameters")
+    s.close()
+
+
 # ---- 4. divergence is an outcome, not a fault ---------------------------------------------------
 def test_diverged_samples_stop_alone():
     """Sample 1 starts beyond the 1e6 bound and sample 2 carries a NaN: arithmetic only.  Both stop
