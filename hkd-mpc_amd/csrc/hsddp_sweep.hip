@@ -40,6 +40,10 @@
 // the two waves of the column split for small batches (k_riccati_cs), which share one element pair
 // and each form half of the columns.
 //
+// The one-wave sweep's knot loops are functions of their own (phase_knots_masked), one with the
+// runtime contact mask and one for each of the two trot masks, which issue only the structurally
+// non-zero multiply-adds of B_c and of A - I's omega rows (HSDDP_SWEEP_MASKS=0: runtime mask only).
+//
 // Templates on `real`: double (the reference's T = double) and float (config C5's fp32 mode).
 #include "hsddp_wave.h"
 
@@ -165,14 +169,20 @@ template <> struct Prec<float> {
     static constexpr int LQS = LQW32;
 };
 
+// A pointer to global memory, typed as one: what it addresses stays known (global_* instructions,
+// counted by vmcnt alone) in code that does not see the kernel arguments it came from
+// (phase_knots_masked).
+template <typename T>
+using Global = __attribute__((address_space(1))) T *;
+
 // One sweep item: element, regularisation, outputs (gain rows, dU rows) and whether it runs.
 template <typename real>
 struct Item {
     int b;          // element (valid even when inactive: its rows are read, never written)
     bool act;       // this half sweeps
     real reg;
-    real *K;        // [Kc][12][24]
-    double *dU;     // [Kc][24]
+    Global<real> K;     // [Kc][12][24]
+    Global<double> dU;  // [Kc][24]
 };
 
 // Per-lane constants of a phase (contacts of the lane's item); the B entries of the contacts
@@ -286,6 +296,7 @@ struct Lane {
     int rb[3];      // image index of this Quu column's ReB row (leg pos / 3, axis pos % 3)
     int xc0, xkind;  // lxx cross terms of row pp: kind 1 (rows 3..5): columns xc0 + 3 t; kind 2 (rows >= 12): xc0
 };
+DEV Lane make_lane();
 
 // Column split: wave W of k_riccati_cs forms the entries of M, Z, Qxx and H in the columns c with
 // cs_wave(c) == W.  The two sets of 12 balance the structural multiply-adds of M = H A (and of
@@ -299,14 +310,23 @@ DEV constexpr bool cs_mine(int c) { return W < 0 || cs_wave(c) == W; }
 
 // acc[c] += sum_j x[j] S[j][c] (S = A - I: rows 0..2 eul, 3..5 the dt entries, 6..8 omega) in
 // source order: consecutive multiply-adds feed different accumulators; W >= 0: the columns of
-// wave W only
-template <int W = -1, typename real>
+// wave W only.  MASK >= 0 (the phase's contact mask at compile time): the omega rows' entries in a
+// swing leg's two foot columns are exact zeros (hkd_partial_compact: they carry the factor c_l) and
+// are not issued.
+template <int MASK>
+DEV constexpr bool stance(int l) { return MASK < 0 || ((MASK >> l) & 1); }
+template <int MASK>
+DEV constexpr bool swing(int l) { return MASK < 0 || !((MASK >> l) & 1); }
+template <int MASK>
+DEV constexpr bool sw_live(int q) { return q < 9 || stance<MASK>((q - 9) >> 1); }
+
+template <int W = -1, int MASK = -1, typename real>
 DEV void emit_SA(real (&acc)[NX], const real (&x)[NX], const real (&cf)[8], real dt)
 {
     auto sw_row = [&](auto I) {
         constexpr int i = I;
         static_for<17>([&](auto Q) {
-            if constexpr (cs_mine<W>(sw_col(Q))) vfma<sw_at(i, Q)>(acc[sw_col(Q)], cf, x[6 + i]);
+            if constexpr (cs_mine<W>(sw_col(Q)) && sw_live<MASK>(Q)) vfma<sw_at(i, Q)>(acc[sw_col(Q)], cf, x[6 + i]);
         });
     };
     auto se_row = [&](auto I) {
@@ -329,17 +349,27 @@ DEV void emit_SA(real (&acc)[NX], const real (&x)[NX], const real (&cf)[8], real
 // acc[q] += (B_c^T y)[q] for the 12 coupled controls, y = (y6, y7, y8) on B's omega rows (BW, DPP
 // broadcast), y9[a] on row 9 + a (bv: dt c / m), y12[q] on row 12 + q (bq: dt (1 - c)); the
 // structurally absent half of the last two is an exact zero.  Controls Q0 .. Q1 - 1 only.
-template <int Q0 = 0, int Q1 = HC, typename real>
+// MASK >= 0: only the structural terms are issued — a stance leg's controls (its GRF) keep bv and
+// BW, a swing leg's (its joint velocities) keep bq; the omitted terms multiply by exact zeros.
+template <int Q0 = 0, int Q1 = HC, int MASK = -1, typename real>
 DEV void emit_Bc(real (&acc)[HC], real y6, real y7, real y8, const real *y9, const real *y12, const real (&bv)[4],
                  const real (&bq)[4], const real (&cf)[8])
 {
 #pragma unroll
-    for (int q = Q0; q < Q1; ++q) acc[q] = __builtin_fma(y12[q], bq[q / 3], acc[q]);
+    for (int q = Q0; q < Q1; ++q)
+        if (swing<MASK>(q / 3)) acc[q] = __builtin_fma(y12[q], bq[q / 3], acc[q]);
 #pragma unroll
-    for (int q = Q0; q < Q1; ++q) acc[q] = __builtin_fma(y9[q % 3], bv[q / 3], acc[q]);
-    static_for<Q1 - Q0>([&](auto Q) { vfma<bw_at(0, Q0 + Q)>(acc[Q0 + Q], cf, y6); });
-    static_for<Q1 - Q0>([&](auto Q) { vfma<bw_at(1, Q0 + Q)>(acc[Q0 + Q], cf, y7); });
-    static_for<Q1 - Q0>([&](auto Q) { vfma<bw_at(2, Q0 + Q)>(acc[Q0 + Q], cf, y8); });
+    for (int q = Q0; q < Q1; ++q)
+        if (stance<MASK>(q / 3)) acc[q] = __builtin_fma(y9[q % 3], bv[q / 3], acc[q]);
+    static_for<Q1 - Q0>([&](auto Q) {
+        if constexpr (stance<MASK>((Q0 + Q) / 3)) vfma<bw_at(0, Q0 + Q)>(acc[Q0 + Q], cf, y6);
+    });
+    static_for<Q1 - Q0>([&](auto Q) {
+        if constexpr (stance<MASK>((Q0 + Q) / 3)) vfma<bw_at(1, Q0 + Q)>(acc[Q0 + Q], cf, y7);
+    });
+    static_for<Q1 - Q0>([&](auto Q) {
+        if constexpr (stance<MASK>((Q0 + Q) / 3)) vfma<bw_at(2, Q0 + Q)>(acc[Q0 + Q], cf, y8);
+    });
 }
 
 // Gaussian elimination without pivoting on the columns held in lanes, then back substitution:
@@ -438,8 +468,8 @@ DEV void eliminate(real (&w)[HC], real (&w2)[HC], unsigned long long &bad)
 // the other wave's H columns read.  ib: the image buffer of this knot (the next knot's go to
 // ib ^ 1); par: which MZ image holds M (the other takes Z).  Both waves run the same branch
 // decisions (live, the PSD test) on equal values.
-template <int W, bool DV, typename real, typename LdsT>
-DEV void knot(const Params &p, LdsT &S, const Lane &L, const Phase<real> &ph, const Item<real> &it, int kc,
+template <int W, bool DV, int MASK = -1, typename real, typename LdsT>
+DEV void knot(real dt, LdsT &S, const Lane &L, const Phase<real> &ph, const Item<real> &it, int kc,
               real (&h)[NX], real &g, bool &live, bool first, bool more, int ib, int par, const real *nrec0,
               const real *ndef0, const real *nrec1, const real *ndef1, double &dvs)
 {
@@ -461,8 +491,8 @@ DEV void knot(const Params &p, LdsT &S, const Lane &L, const Phase<real> &ph, co
     auto MA = [&]() -> real * { if constexpr (CS) return ma; else return I.MI; };
     auto ZA = [&]() -> real * { if constexpr (CS) return za; else return I.MI; };
     const int pp = L.pp, pos = L.pos;
-    const real dt = (real)p.dt;
     const real reg = it.reg;
+    const int cmask = MASK >= 0 ? MASK : ph.cmask;  // (MASK >= 0: the selects on it fold)
     if constexpr (!CS) STAMP(0);
     // this knot's images: a phase's first knot waits for them here (split: each wave for its own
     // requests, then both), every other knot's landed before the previous knot's output stores (end
@@ -485,7 +515,7 @@ DEV void knot(const Params &p, LdsT &S, const Lane &L, const Phase<real> &ph, co
     real t[HC], ga[4] = {g, 0, 0, 0};
 #pragma unroll
     for (int q = 0; q < HC; ++q) t[q] = 0;
-    emit_Bc<Q0, Q1>(t, h[6], h[7], h[8], h + 9, h + 12, bv, bq, cf);
+    emit_Bc<Q0, Q1, MASK>(t, h[6], h[7], h[8], h + 9, h + 12, bv, bq, cf);
     static_for<NX>([&](auto C) { vfma<V_D + C>(ga[C & 3], cf, h[C]); });
     const real gn = (ga[0] + ga[1]) + (ga[2] + ga[3]);
     pin(t);
@@ -496,7 +526,7 @@ DEV void knot(const Params &p, LdsT &S, const Lane &L, const Phase<real> &ph, co
     for (int j = 9; j < NX; ++j) h9[j] = 0;
     SSYNC();
     real (&m)[NX] = h;
-    emit_SA<W>(m, h9, cf, dt);
+    emit_SA<W, MASK>(m, h9, cf, dt);
     pin(t);
     pin(m);
     if (L.row) {
@@ -518,13 +548,13 @@ DEV void knot(const Params &p, LdsT &S, const Lane &L, const Phase<real> &ph, co
     real w2[HC];
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
-        const real *lcp = pp == NX ? img + V_LU + (((ph.cmask >> l) & 1) ? 3 * l : 12 + 3 * l) : S.zero;
+        const real *lcp = pp == NX ? img + V_LU + (((cmask >> l) & 1) ? 3 * l : 12 + 3 * l) : S.zero;
 #pragma unroll
         for (int a = 0; a < 3; ++a) w2[3 * l + a] = lcp[a];
     }
     // Z[pp][i] = M[pp][i] + sum_k M[k][pp] S[k][i] (S^T M transposed); position 24: (S^T Gn)[i]
-    emit_SA<W>(m, mc, cf, dt);
-    emit_Bc(w2, mc[6], mc[7], mc[8], mc + 9, mc + 12, bv, bq, cf);
+    emit_SA<W, MASK>(m, mc, cf, dt);
+    emit_Bc<0, HC, MASK>(w2, mc[6], mc[7], mc[8], mc + 9, mc + 12, bv, bq, cf);
     pin(m);
     pin(w2);
     if constexpr (!CS) STAMP(3);
@@ -553,7 +583,7 @@ DEV void knot(const Params &p, LdsT &S, const Lane &L, const Phase<real> &ph, co
         }
     }
     if constexpr (CS) CSYNC(); else SSYNC();
-    const real *zrow = L.row ? ZA() + pp * MS : S.zero;
+    const real *zrow = (const real *)__builtin_assume_aligned(L.row ? ZA() + pp * MS : S.zero, 16);
     real qxx[NX], zc[NX];
     if constexpr (CS) {
         static_for<NX>([&](auto C) {
@@ -596,11 +626,11 @@ DEV void knot(const Params &p, LdsT &S, const Lane &L, const Phase<real> &ph, co
     real w[HC];
 #pragma unroll
     for (int q = 0; q < HC; ++q) w[q] = (L.qlane && lq == q / 3) ? lbr[q % 3] : (real)0;
-    emit_Bc(w, tcol[0], tcol[1], tcol[2], tcol + 3, tcol + 6, bv, bq, cf);
+    emit_Bc<0, HC, MASK>(w, tcol[0], tcol[1], tcol[2], tcol + 3, tcol + 6, bv, bq, cf);
     pin(w);
     // decoupled controls on positions 0..11: Qu_z = lu_z, Quu_zz = dt R_z + reg
     const bool zl = pp < HC;
-    const int du_z = ((ph.cmask >> ((zl ? pp : 0) / 3)) & 1) ? 12 + pp : pp;  // the decoupled control of pp < 12
+    const int du_z = ((cmask >> ((zl ? pp : 0) / 3)) & 1) ? 12 + pp : pp;  // the decoupled control of pp < 12
     const real quz = img[zl ? V_LU + du_z : V_LU];
     const real qzz = ph.dtrz + reg;
     // the images are read: the next knot's are requested now (in flight during the elimination;
@@ -629,7 +659,7 @@ DEV void knot(const Params &p, LdsT &S, const Lane &L, const Phase<real> &ph, co
     // write the same values) ---------------------------------------------------------------------
     if (pp == NX)  // coupled dU from position 24
 #pragma unroll
-        for (int q = 0; q < HC; ++q) I.du[(((ph.cmask >> (q / 3)) & 1) ? 0 : 12) + q] = w2[q];
+        for (int q = 0; q < HC; ++q) I.du[(((cmask >> (q / 3)) & 1) ? 0 : 12) + q] = w2[q];
     if (zl) I.du[du_z] = -(quz / qzz);
     SSYNC();
     // K_c columns of both DPP rows at every DPP position (column c of the item on position c & 15
@@ -691,7 +721,7 @@ DEV void knot(const Params &p, LdsT &S, const Lane &L, const Phase<real> &ph, co
     // rows of the item (the two write the same value), columns 16..23 from kb.  Split: wave 0 stores
     // columns 0..15, wave 1 columns 16..23 and dU.
     if (st) {
-        real *Kg = it.K + (size_t)kc * KCW;
+        const Global<real> Kg = it.K + (size_t)kc * KCW;
         if constexpr (W <= 0) {
 #pragma unroll
             for (int q = 0; q < HC; ++q) Kg[q * NX + pos] = ka[q];
@@ -714,13 +744,116 @@ DEV void knot(const Params &p, LdsT &S, const Lane &L, const Phase<real> &ph, co
     if constexpr (!CS) STAMP(9);
 }
 
+// The knots of one phase, last to first, for the wave's two items: the request for the last knot's
+// images (which that knot waits for), then the knot loop with the next knot's images requested a
+// knot ahead.  rec* / def*: each item's record of the phase's knot 0 and its Defect[1]; kc0: the
+// phase's first control slot.  fail: the control slot at which this half's PSD test failed.  The
+// loop ends early once neither half is live.  MASK: the phase's contact mask at compile time
+// (knot<W, DV, MASK>), -1: read from ph.
+template <int MASK, int CSW, bool DV, typename real, typename LdsT>
+DEV void phase_knots(real dt, LdsT &S, const Lane &L, const Phase<real> &ph, const Item<real> &it, int N, int kc0,
+                     const real *rec0, const real *def0, const real *rec1, const real *def1, real (&h)[NX], real &g,
+                     bool &live, int &fail, double &dvs, int &ib, int &par)
+{
+    constexpr bool CS = CSW >= 0;
+    constexpr int LQS = Prec<real>::LQS;
+    if constexpr (CS) fetch_cs<CSW>(S, ib, rec0 + (size_t)(N - 1) * LQS, def0 + (size_t)(N - 1) * NX, rec1 + (size_t)(N - 1) * LQS,
+                                    def1 + (size_t)(N - 1) * NX, L.lane);
+    else fetch(S, rec0 + (size_t)(N - 1) * LQS, def0 + (size_t)(N - 1) * NX, rec1 + (size_t)(N - 1) * LQS,
+               def1 + (size_t)(N - 1) * NX, L.lane);
+    int k = N - 1;
+#pragma unroll 1
+    for (; k >= 0; --k) {
+        const bool more = k > 0;
+        const int kn = more ? k - 1 : 0;
+        const bool was = live;
+        knot<CSW, DV, MASK>(dt, S, L, ph, it, kc0 + k, h, g, live, k == N - 1, more, ib, par, rec0 + (size_t)kn * LQS,
+                            def0 + (size_t)kn * NX, rec1 + (size_t)kn * LQS, def1 + (size_t)kn * NX, dvs);
+        if constexpr (CS) {
+            ib ^= more ? 1 : 0;
+            par ^= 1;
+        }
+        if (was && !live) fail = kc0 + k;
+        if (!__builtin_amdgcn_ballot_w64(live)) break;
+    }
+}
+
+// The contact masks with a knot loop of their own: the two diagonal pairs a trot alternates between
+// (legs FR, FL, HR, HL = bits 0..3 of Phase::cmask, in the order of the contacts array: FR + HL and
+// FL + HR).  Every other mask (pace, bound, flight, full stance) takes the runtime-mask loop.
+constexpr int MASK_TROT_A = (1 << 0) | (1 << 3), MASK_TROT_B = (1 << 1) | (1 << 2);
+
+// The scalar sweep state of a half that a phase's knot loop advances.
+struct PhaseOut {
+    double dvs;
+    int live, fail;
+};
+
+template <typename T>
+DEV T *uniform_ptr(T *q)
+{
+    const size_t v = (size_t)q;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return (T *)(((size_t)hi << 32) | lo);
+}
+
+// phase_knots<MASK> as a function of its own (the one-wave sweep's knot loops): a second inlined
+// copy of the knot loop makes the register allocator spill inside every copy (DESIGN.md §8, round
+// 5); out of line, every loop — the two specialised ones and the runtime-mask one, MASK = -1 — is
+// allocated alone.  The state crosses the call once per phase: H row pp and G[pp] in the item's M
+// image (row pp, columns 0..24: free between phases), dvs / live / fail in *io, a local of the
+// caller (a call that is handed the address of a caller's local is not a tail-call candidate, and
+// only then does the callee skip saving callee-saved registers: 73 dword stores and loads per lane
+// and phase otherwise), everything else in registers — the arguments arrive in VGPRs and the
+// wave-uniform ones are moved back to SGPRs.  flags: Phase::cmask
+// (bits 0..3), Phase::xmask (bits 4..7).  WPE: the callers' waves per SIMD (their
+// register budget, which the loops inherit from the kernels that call them).
+template <int MASK, bool DV, int WPE, typename real>
+__device__ __attribute__((noinline)) void phase_knots_masked(unsigned lds, int flags, real lxd, real xw, real dtr,
+                                                             real dtrz, real reg, Global<real> K, Global<double> dU,
+                                                             real dt, int N, int k0, const real *rec0, const real *def0,
+                                                             const real *rec1, const real *def1, PhaseOut *io)
+{
+    // (the LDS address space and alignment restated: the kernel's code knows them from its __shared__
+    // variable, and forms ds_* instructions, 16 bytes wide where it can, with them)
+    typedef __attribute__((address_space(3))) Lds<real> *LdsPtr;
+    static_assert(alignof(Lds<real>) == 16, "the masked address bits");
+    Lds<real> &S = *(Lds<real> *)(LdsPtr)(size_t)(__builtin_amdgcn_readfirstlane(lds) & ~15u);
+    const Lane L = make_lane();
+    Phase<real> ph;
+    ph.cmask = MASK >= 0 ? MASK : (flags & 15);
+    ph.xmask = (flags >> 4) & 15; ph.lxd = lxd; ph.xw = xw; ph.dtr = dtr; ph.dtrz = dtrz;
+    Item<real> it;
+    it.b = 0; it.act = true; it.reg = reg; it.K = K; it.dU = dU;
+    real *row = S.it[L.e].MI + L.pp * MS;
+    real h[NX], g = L.row ? row[NX] : (real)0;
+#pragma unroll
+    for (int j = 0; j < NX; ++j) h[j] = L.row ? row[j] : (real)0;
+    SSYNC();
+    double dvs = io->dvs;
+    bool live = io->live != 0;
+    int fail = io->fail, ib = 0, par = 0;
+    phase_knots<MASK, -1, DV>(uniform(dt), S, L, ph, it, __builtin_amdgcn_readfirstlane(N), __builtin_amdgcn_readfirstlane(k0),
+                              uniform_ptr(rec0), uniform_ptr(def0), uniform_ptr(rec1), uniform_ptr(def1), h, g, live, fail,
+                              dvs, ib, par);
+    if (L.row) {
+#pragma unroll
+        for (int j = 0; j < NX; ++j) row[j] = h[j];
+        row[NX] = g;
+    }
+    SSYNC();
+    io->dvs = dvs; io->live = live; io->fail = fail;
+}
+
 // MultiPhaseDDP::backward_sweep (MultiPhaseDDP.cpp:190-229) for the wave's two items with their
 // own regularisation.  Returns, per half, -1 (success) or the control slot of the first knot whose
 // Quu fails the PSD test (that knot and the ones below it are not written).  DV: dv = the half's
 // sum over every knot of Qu^T dU (= dV_1 = -dV_2 of the sweep, SinglePhase.cpp:359-362,
-// MultiPhaseDDP.cpp:224-226), on every lane of the half.
-template <typename real, bool EL, bool DV, int CSW = -1, typename LdsT = Lds<real>>
-DEV int sweep_pair(const Params &p, const Bufs &d, LdsT &S, const Lane &L, const Item<real> &it, double &dv)
+// MultiPhaseDDP.cpp:224-226), on every lane of the half.  masks (wave-uniform; the one-wave sweep
+// only): phases may take the loops specialised on their contact mask (sweep_masks).
+template <typename real, bool EL, bool DV, int CSW = -1, int WPE = 2, typename LdsT = Lds<real>>
+DEV int sweep_pair(const Params &p, const Bufs &d, LdsT &S, const Lane &L, const Item<real> &it, double &dv,
+                   bool masks = false)
 {
     constexpr bool CS = CSW >= 0;  // wave CSW of the column split (k_riccati_cs)
     int ib = 0, par = 0;           // (CS) image buffer, M / Z image roles
@@ -809,25 +942,41 @@ DEV int sweep_pair(const Params &p, const Bufs &d, LdsT &S, const Lane &L, const
             if constexpr (CS) CSYNC();
         }
         const int N = PL.N(i), s0 = PL.s0(i), k0 = PL.k0(i);
-        auto recp = [&](int bb, int k) { return lqg + ((size_t)bb * p.Kc + k0 + k) * Prec<real>::LQS; };
-        auto defp0 = [&](int k) { return defg0 + ((size_t)b0 * p.S + s0 + k + 1) * NX; };
-        auto defp1 = [&](int k) { return defg1 + ((size_t)b1 * p.S + s0 + k + 1) * NX; };
-        if constexpr (CS) fetch_cs<CSW>(S, ib, recp(b0, N - 1), defp0(N - 1), recp(b1, N - 1), defp1(N - 1), L.lane);
-        else fetch(S, recp(b0, N - 1), defp0(N - 1), recp(b1, N - 1), defp1(N - 1), L.lane);
-        int k = N - 1;
-#pragma unroll 1
-        for (; k >= 0; --k) {
-            const bool more = k > 0;
-            const int kn = more ? k - 1 : 0;
-            const bool was = live;
-            knot<CSW, DV>(p, S, L, ph, it, k0 + k, h, g, live, k == N - 1, more, ib, par, recp(b0, kn), defp0(kn),
-                          recp(b1, kn), defp1(kn), dvs);
-            if constexpr (CS) {
-                ib ^= more ? 1 : 0;
-                par ^= 1;
+        // the phase's knot 0 of each item: its record and Defect[1]
+        const real *rec0 = lqg + ((size_t)b0 * p.Kc + k0) * Prec<real>::LQS, *def0 = defg0 + ((size_t)b0 * p.S + s0 + 1) * NX;
+        const real *rec1 = lqg + ((size_t)b1 * p.Kc + k0) * Prec<real>::LQS, *def1 = defg1 + ((size_t)b1 * p.S + s0 + 1) * NX;
+        // the phase's knots.  One-wave sweep, multiple shooting: out of line (phase_knots_masked), the
+        // loop with the contact mask compiled in when both halves are live on one instantiated mask,
+        // else the runtime-mask loop.  Column split and single shooting: the runtime-mask loop, inlined.
+        if constexpr (CS || DV) {
+            // (single shooting keeps its inlined loop: out of line its full solves differed from the
+            // column split's, test_gpu_sweep_split.py::test_split_single_shooting, cause not found)
+            phase_knots<-1, CSW, DV>((real)p.dt, S, L, ph, it, N, k0, rec0, def0, rec1, def1, h, g, live, fail, dvs, ib, par);
+        } else {
+            // H row pp and G[pp] cross in the item's M image, the rest in registers
+            real *row = S.it[L.e].MI + pp * MS;
+            if (L.row) {
+#pragma unroll
+                for (int c = 0; c < NX; ++c) row[c] = h[c];
+                row[NX] = g;
             }
-            if (was && !live) fail = k0 + k;
-            if (!__builtin_amdgcn_ballot_w64(live)) break;
+            SSYNC();
+            const int m0 = __builtin_amdgcn_readlane(ph.cmask, 0), m1 = __builtin_amdgcn_readlane(ph.cmask, 32);
+            const bool both = masks && m0 == m1 && __builtin_amdgcn_ballot_w64(live) == ~0ull;
+            const int flags = ph.cmask | (ph.xmask << 4);
+            PhaseOut o{dvs, live, fail};
+#define HSDDP_PHASE(MASK)                                                                                              \
+    phase_knots_masked<MASK, DV, WPE, real>((unsigned)(size_t)&S, flags, ph.lxd, ph.xw, ph.dtr, ph.dtrz, it.reg, it.K, \
+                                            it.dU, (real)p.dt, N, k0, rec0, def0, rec1, def1, &o)
+            if (both && m0 == MASK_TROT_A) HSDDP_PHASE(MASK_TROT_A);
+            else if (both && m0 == MASK_TROT_B) HSDDP_PHASE(MASK_TROT_B);
+            else HSDDP_PHASE(-1);
+#undef HSDDP_PHASE
+            dvs = o.dvs; live = o.live != 0; fail = o.fail;
+#pragma unroll
+            for (int c = 0; c < NX; ++c) h[c] = L.row ? row[c] : (real)0;
+            g = L.row ? row[NX] : (real)0;
+            SSYNC();
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA left in flight
         if (!__builtin_amdgcn_ballot_w64(live)) break;
@@ -966,7 +1115,7 @@ using namespace sweep;
 // parallel retry cannot take) mu = max(mu * update_regularization, 1e-3) until a sweep succeeds or
 // mu > 1e2, then mu / 20 (0 below 1e-6) as the next regularisation.
 template <typename real, bool EL, bool DV, int WPB>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB == 2 ? SWEEP_WPB2_WPE : 2))) void k_riccati(Params p, Bufs d)
+__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB == 2 ? SWEEP_WPB2_WPE : 2))) void k_riccati(Params p, Bufs d, int masks)
 {
     // WPB independent waves per workgroup, each with its own LDS and element pair (no barrier couples
     // them; sweep_wpb)
@@ -998,15 +1147,15 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB ==
     double reg = E.reg;
     Item<real> it;
     it.b = bv;
-    it.K = Prec<real>::K(d) + (size_t)bv * p.Kc * KCW;
-    it.dU = d.dU + (size_t)bv * p.Kc * NX;
+    it.K = (Global<real>)(Prec<real>::K(d) + (size_t)bv * p.Kc * KCW);
+    it.dU = (Global<double>)(d.dU + (size_t)bv * p.Kc * NX);
     bool need = act, ok = false;
     double dvk = 0.0;  // DV: Qu^T dU summed over the successful sweep
     for (int attempt = 0; __builtin_amdgcn_ballot_w64(need); ++attempt) {
         it.act = need;
         it.reg = (real)reg;
         double dv;
-        const int fk = sweep_pair<real, EL, DV>(p, d, S, L, it, dv);
+        const int fk = sweep_pair<real, EL, DV, -1, (WPB == 2 ? SWEEP_WPB2_WPE : 2)>(p, d, S, L, it, dv, masks != 0);
         if (need) {
             if (fk < 0) {
                 ok = true;
@@ -1080,8 +1229,8 @@ DEV void riccati_cs_wave(const Params &p, const Bufs &d, LdsCS<double> &S)
     double reg = E.reg;
     Item<real> it;
     it.b = bv;
-    it.K = d.K + (size_t)bv * p.Kc * KCW;
-    it.dU = d.dU + (size_t)bv * p.Kc * NX;
+    it.K = (Global<real>)(d.K + (size_t)bv * p.Kc * KCW);
+    it.dU = (Global<double>)(d.dU + (size_t)bv * p.Kc * NX);
     bool need = act, ok = false;
     double dvk = 0.0;  // DV: Qu^T dU summed over the successful sweep
     for (int attempt = 0; __builtin_amdgcn_ballot_w64(need); ++attempt) {
@@ -1141,7 +1290,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
 // rows, two items per wave.  Every attempt is the sweep the sequential loop would run with that mu,
 // so taking the first success (k_riccati_select) gives the loop's result.
 template <typename real, bool EL, bool DV>
-__global__ __launch_bounds__(64, 2) void k_riccati_retry(Params p, Bufs d)
+__global__ __launch_bounds__(64, 2) void k_riccati_retry(Params p, Bufs d, int masks)
 {
     __shared__ Lds<real> S;
     const Lane L = make_lane();
@@ -1169,10 +1318,10 @@ __global__ __launch_bounds__(64, 2) void k_riccati_retry(Params p, Bufs d)
     it.b = e.b;
     it.act = act;
     it.reg = (real)reg;
-    it.K = (real *)d.retry_K + slot * p.Kc * KCW;
-    it.dU = d.retry_dU + slot * p.Kc * NX;
+    it.K = (Global<real>)((real *)d.retry_K + slot * p.Kc * KCW);
+    it.dU = (Global<double>)(d.retry_dU + slot * p.Kc * NX);
     double dv;
-    const int fk = sweep_pair<real, EL, DV>(p, d, S, L, it, dv);
+    const int fk = sweep_pair<real, EL, DV>(p, d, S, L, it, dv, masks != 0);
     if (act && L.pp == 0) *flag = fk < 0 ? 1 : -1 - fk;  // success, or -1 - (the failing control slot)
     if (DV && act && L.pp == 0) d.retry_dv[slot] = dv;
 }
@@ -1272,6 +1421,14 @@ static bool sweep_split(const Params &p)
 // 4096): two per workgroup 0.866 / 0.883 / 1.29 / 1.61, one 0.812 / 0.913 / 1.36 / 1.59 — a
 // workgroup's two waves go to different SIMDs of one CU, which the single-wave workgroups of a
 // half-full launch do not reliably do.
+// the knot loops specialised on a phase's contact mask (phase_knots_masked) in k_riccati and
+// k_riccati_retry; HSDDP_SWEEP_MASKS = 0 keeps every phase on the runtime-mask loop (tests, A/B)
+static int sweep_masks()
+{
+    const char *e = std::getenv("HSDDP_SWEEP_MASKS");
+    return e && *e == '0' ? 0 : 1;
+}
+
 static int sweep_wpb(const Params &p)
 {
     if (p.fp32) return 1;
@@ -1289,23 +1446,23 @@ void launch_riccati(const Params &p, const Bufs &d, hipStream_t st)
 #define HSDDP_RIC(kern, grid, real)                                                                          \
     do {                                                                                                     \
         if (p.ms0) {                                                                                         \
-            if (p.elem_layout) hipLaunchKernelGGL((kern<real, true, true>), grid, dim3(64), 0, st, p, d);      \
-            else hipLaunchKernelGGL((kern<real, false, true>), grid, dim3(64), 0, st, p, d);                   \
+            if (p.elem_layout) hipLaunchKernelGGL((kern<real, true, true>), grid, dim3(64), 0, st, p, d, masks); \
+            else hipLaunchKernelGGL((kern<real, false, true>), grid, dim3(64), 0, st, p, d, masks);            \
         } else {                                                                                             \
-            if (p.elem_layout) hipLaunchKernelGGL((kern<real, true, false>), grid, dim3(64), 0, st, p, d);     \
-            else hipLaunchKernelGGL((kern<real, false, false>), grid, dim3(64), 0, st, p, d);                  \
+            if (p.elem_layout) hipLaunchKernelGGL((kern<real, true, false>), grid, dim3(64), 0, st, p, d, masks); \
+            else hipLaunchKernelGGL((kern<real, false, false>), grid, dim3(64), 0, st, p, d, masks);           \
         }                                                                                                    \
     } while (0)
-    const int wpb = sweep_wpb(p);
+    const int wpb = sweep_wpb(p), masks = sweep_masks();
     const dim3 gw((unsigned)(((p.elem_layout ? p.n_pairs : (p.B + 1) / 2) + wpb - 1) / wpb));
 #define HSDDP_RIC_W(real, W)                                                                                   \
     do {                                                                                                       \
         if (p.ms0) {                                                                                           \
-            if (p.elem_layout) hipLaunchKernelGGL((k_riccati<real, true, true, W>), gw, dim3(64 * W), 0, st, p, d);  \
-            else hipLaunchKernelGGL((k_riccati<real, false, true, W>), gw, dim3(64 * W), 0, st, p, d);               \
+            if (p.elem_layout) hipLaunchKernelGGL((k_riccati<real, true, true, W>), gw, dim3(64 * W), 0, st, p, d, masks);  \
+            else hipLaunchKernelGGL((k_riccati<real, false, true, W>), gw, dim3(64 * W), 0, st, p, d, masks);        \
         } else {                                                                                               \
-            if (p.elem_layout) hipLaunchKernelGGL((k_riccati<real, true, false, W>), gw, dim3(64 * W), 0, st, p, d); \
-            else hipLaunchKernelGGL((k_riccati<real, false, false, W>), gw, dim3(64 * W), 0, st, p, d);              \
+            if (p.elem_layout) hipLaunchKernelGGL((k_riccati<real, true, false, W>), gw, dim3(64 * W), 0, st, p, d, masks); \
+            else hipLaunchKernelGGL((k_riccati<real, false, false, W>), gw, dim3(64 * W), 0, st, p, d, masks);       \
         }                                                                                                      \
     } while (0)
     if (p.fp32) HSDDP_RIC_W(float, 1);
