@@ -89,7 +89,9 @@ static void fill_params(hsddp_handle h)
 // initial one and one per inner iteration (MultiPhaseDDP.cpp:277-280, 368-371)
 static int ensure_history(hsddp_handle h)
 {
-    const long need = 1 + (long)std::max(0, h->opt.max_AL_iter) * std::max(0, h->opt.max_DDP_iter);
+    // (with per-element budgets: the largest element's too)
+    const long need = std::max(1 + (long)std::max(0, h->opt.max_AL_iter) * std::max(0, h->opt.max_DDP_iter),
+                               h->budgets_on ? 1 + h->bud_hist : 0L);
     if (h->hist && need <= h->p.hcap) return HSDDP_OK;
     const int cap = (int)std::min<long>(std::max<long>(need, 16), 1 << 20);
     float *nh = nullptr;
@@ -286,6 +288,55 @@ extern "C" int hsddp_set_options(hsddp_handle h, const hsddp_options *o)
     return HSDDP_OK;
 }
 
+// MultiPhaseDDP::solve's loop bounds (MultiPhaseDDP.cpp:257, 304) per element: the bounds go to the
+// device array the decision kernels read (hsddp_internal.h); the host loops to the largest.
+extern "C" int hsddp_set_element_budgets(hsddp_handle h, const int *max_AL_iter, const int *max_DDP_iter)
+{
+    if (!h) return fail(HSDDP_ERR_ARG, "null handle");
+    if (!max_AL_iter && !max_DDP_iter) {  // back to the handle-wide options
+        h->budgets_on = false;
+        return HSDDP_OK;
+    }
+    if (!max_AL_iter || !max_DDP_iter) return fail(HSDDP_ERR_ARG, "budgets: both arrays or neither");
+    const int B = h->p.B;
+    std::vector<int> bud((size_t)B * 2);
+    int al = 0, ddp = 0;
+    long hist = 0;
+    for (int b = 0; b < B; ++b) {
+        if (max_AL_iter[b] < 0 || max_DDP_iter[b] < 0) return fail(HSDDP_ERR_ARG, "negative iteration budget");
+        if ((long)max_AL_iter[b] * max_DDP_iter[b] >= (1L << 20))
+            return fail(HSDDP_ERR_ARG, "max_AL_iter * max_DDP_iter exceeds the solver-info history (2^20 entries)");
+        bud[2 * b] = max_AL_iter[b];
+        bud[2 * b + 1] = max_DDP_iter[b];
+        al = std::max(al, max_AL_iter[b]);
+        ddp = std::max(ddp, max_DDP_iter[b]);
+        hist = std::max(hist, (long)max_AL_iter[b] * max_DDP_iter[b]);
+    }
+    HIPCHK(hipSetDevice(h->desc.device));
+    int rc;
+    if (!h->budgets) {
+        if ((rc = dalloc(h, h->budgets, (size_t)B * 2))) {
+            h->budgets = nullptr;
+            (void)hipGetLastError();
+            return rc;
+        }
+    }
+    const bool was = h->budgets_on;
+    const long hist_was = h->bud_hist;
+    h->budgets_on = true;
+    h->bud_hist = hist;
+    if ((rc = ensure_history(h))) {  // allocation failed: the handle keeps what it had
+        h->budgets_on = was;
+        h->bud_hist = hist_was;
+        return rc;
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(h->budgets, bud.data(), bud.size() * sizeof(int), hipMemcpyHostToDevice));
+    h->bud_AL = al;
+    h->bud_DDP = ddp;
+    return HSDDP_OK;
+}
+
 void hsddp::adopt_shared_layout(hsddp_handle h, const Layout &L, const int *reach)
 {
     Params &p = h->p;
@@ -329,8 +380,12 @@ int hsddp::set_layouts(hsddp_handle h, const std::vector<Layout> &lays)
     HIPCHK(hipMemcpy((void *)h->d.lay, lays.data(), B * sizeof(Layout), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy((void *)h->d.pairs, pairs.data(), pairs.size() * sizeof(int), hipMemcpyHostToDevice));
     h->lays = lays;
+    h->pair_of.assign(B, -1);
+    for (size_t q = 0; q < pairs.size(); ++q)
+        if (pairs[q] >= 0) h->pair_of[pairs[q]] = (int)(q / 2);
+    h->pairs_host.swap(pairs);
     p.elem_layout = 1;
-    p.n_pairs = (int)pairs.size() / 2;
+    p.n_pairs = (int)h->pairs_host.size() / 2;
     p.P = Pmax;  // strides of the per-phase and per-slot buffers
     p.S = Smax;
     p.has_tail = tail;
@@ -379,6 +434,14 @@ extern "C" int hsddp_get_element_layouts(hsddp_handle h, int *n_phases, int *hor
             if (reach_end) reach_end[b * HSDDP_MAX_PHASES + i] = in ? reach_of(h, b)[i] : 0;
         }
     }
+    return HSDDP_OK;
+}
+
+extern "C" int hsddp_get_strides(hsddp_handle h, int *n_phases, int *state_slots)
+{
+    if (!h) return fail(HSDDP_ERR_ARG, "null handle");
+    if (n_phases) *n_phases = h->p.P;
+    if (state_slots) *state_slots = h->p.S;
     return HSDDP_OK;
 }
 

@@ -48,6 +48,7 @@ struct hsddp_handle_t {
         Params p;
         Bufs d;
         double alpha = 0;
+        const int *budget = nullptr;
         int par = 0;  // which host count slot (host_counter[8 + 4 * par + 1]) its copy fills
     } iter_graph[8];
     int iter_graph_next = 0;
@@ -94,6 +95,9 @@ struct hsddp_handle_t {
     std::vector<int> win_start;
     int win_len = 0;
     float dt_sim = 0, t_cur = 0;
+    // each element's own clock [B] once hsddp_restart_elements has set some element's back to 0
+    // (empty: the batch shares t_cur)
+    std::vector<float> t_el;
     std::vector<double> durations;
     int retry_cap_alloc = 0, retry_m_alloc = 0;  // parallel regularisation retry scratch (k_riccati_retry)
     float *hist = nullptr;  // solver-info history [B][p.hcap][4] (grown by ensure_history)
@@ -102,6 +106,9 @@ struct hsddp_handle_t {
     Layout shared{};
     std::vector<Layout> lays;
     std::vector<int> reach_el;  // [B][16] is_phase_reach_end per element (with per-element layouts)
+    // host copy of Bufs::pairs [n_pairs][2] and each element's pair (set_layouts; patched in place by
+    // hsddp_restart_elements)
+    std::vector<int> pairs_host, pair_of;
     double *value0 = nullptr;  // G[0], H[0] per phase [B][16][600] (hsddp_set_value_export)
     // asynchronous command extraction (hsddp_extract_commands_async): two device record buffers, two
     // pinned host buffers, a copy stream and per buffer the event of its last copy
@@ -123,6 +130,13 @@ struct hsddp_handle_t {
     // host [B], the handle's own copy of the records' foot placements [B][12] (both allocated on
     // first use), and whether that copy belongs to the current tick (an update with a host-formed or
     // simulated x0 drops it)
+    // per-element iteration budgets (hsddp_set_element_budgets): the device array [B][2] (allocated
+    // on first use), whether it is in force, the largest outer and inner bound (the host's loop
+    // bounds) and the largest outer x inner product (the solver-info history's size)
+    int *budgets = nullptr;
+    bool budgets_on = false;
+    int bud_AL = 0, bud_DDP = 0;
+    long bud_hist = 0;
     hsddp_robot_state *meas_states = nullptr;
     float *meas_feet = nullptr;
     bool meas_held = false;
@@ -156,6 +170,11 @@ inline const int *reach_of(hsddp_handle h, size_t b)
 {
     return h->lays.empty() ? h->reach_end.data() : &h->reach_el[b * HSDDP_MAX_PHASES];
 }
+
+// the budgets the kernels read (null: the handle-wide options) and the host's loop bounds
+inline const int *budget_of(hsddp_handle h) { return h->budgets_on ? h->budgets : nullptr; }
+inline int outer_bound(hsddp_handle h) { return h->budgets_on ? h->bud_AL : h->opt.max_AL_iter; }
+inline int inner_bound(hsddp_handle h) { return h->budgets_on ? h->bud_DDP : h->opt.max_DDP_iter; }
 
 // phase of control slot kc in a layout
 inline int phase_of_control(const Layout &L, int kc)

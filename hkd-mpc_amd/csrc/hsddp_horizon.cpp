@@ -1,18 +1,20 @@
 // hsddp_horizon.cpp — the MPC caller's side of the C-ABI, around the solve: command extraction
 // (HKDMPCSolver::update_foot_placement + publish_mpc_cmd), the receding-horizon shift
 // (HKDProblem::update, HKDProblem.cpp:117-222; its bookkeeping is hsddp_phases.cpp), the reference
-// table and the per-slot references built from it, and hsddp_advance, which steps all of them from
-// the table.
+// table and the per-slot references built from it, hsddp_advance, which steps all of them from
+// the table, and hsddp_restart_elements, which starts single elements again as new problems.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 
 #include "hsddp_handle.h"
 #include "hsddp_mpc.h"
+#include "hsddp_restart.h"
 
 using namespace hsddp;
 
@@ -205,8 +207,9 @@ static std::vector<int> shift_key(const Layout &L, const int *reach, int n_steps
 // touchdown constraints keeps the first ones (the shift is otherwise complete):
 // HSDDP_ERR_UNSUPPORTED, or, with `overflow`, *overflow = 1 and HSDDP_OK (hsddp_advance finishes
 // the step and reports it then).  defer: no synchronisation (one layout for the batch; the flag is
-// read by hsddp_advance).
-static int shift_apply(hsddp_handle h, const ShiftPlan &plan, bool defer, int *overflow)
+// read by hsddp_advance).  zero_u0 = false: a plan of no steps that only moves rows to new strides
+// (hsddp_restart_elements) leaves Ubar[0] as it is.
+static int shift_apply(hsddp_handle h, const ShiftPlan &plan, bool defer, int *overflow, bool zero_u0 = true)
 {
     h->slots_fresh = false;
     Params &p = h->p;
@@ -290,7 +293,7 @@ static int shift_apply(hsddp_handle h, const ShiftPlan &plan, bool defer, int *o
     a.smap = dsm; a.cmap = dcm;
     a.map_id = nk > 1 ? did : nullptr;
     a.fp32 = p.fp32;
-    a.zero_u0 = 1;  // trajectory_ptrs.front()->Ubar[0].setZero() (HKDProblem.cpp:219)
+    a.zero_u0 = zero_u0 ? 1 : 0;  // trajectory_ptrs.front()->Ubar[0].setZero() (HKDProblem.cpp:219)
     a.stage = nullptr;
     if (Snew != p.S) {
         if (!h->shift_stage && (rc = dalloc(h, h->shift_stage, 3 * B * h->S_cap * NX))) return rc;
@@ -423,6 +426,35 @@ extern "C" int hsddp_set_reference_table(hsddp_handle h, const hsddp_quad_state 
     return HSDDP_OK;
 }
 
+// the phases' start times on the float clock of HKDProblem::initialization (t += dt_sim per knot)
+static std::vector<float> clock_starts(const Layout &L, float dt_sim)
+{
+    std::vector<float> start(L.P);
+    float t = 0.0f;
+    for (int i = 0; i < L.P; ++i) {
+        start[i] = t;
+        for (int k = 0; k < L.N[i]; ++k) t += dt_sim;
+    }
+    return start;
+}
+
+// the window sample of every state slot of layout L, S entries (padding slots repeat the last
+// sample): slot times as the reference forms them, t_offset (float, phase start relative to the
+// first phase) + k dt (double), passed on as float (SinglePhase.cpp:243-287; set_time_offset,
+// HKDProblem.cpp:103,208), snapped to a sample (QuadReference.cpp:60-76)
+static std::vector<int> slot_samples(const Layout &L, const std::vector<float> &start, float dt_sim, float dt_ref,
+                                     int sz, int S)
+{
+    std::vector<int> row(S, 0);
+    for (int i = 0; i < L.P; ++i)
+        for (int k = 0; k <= L.N[i]; ++k) {
+            const float t = (float)((double)start[i] + k * (double)dt_sim);
+            row[L.s0[i] + k] = sample_at(t, dt_ref, sz);
+        }
+    for (int sl = L.S; sl < S; ++sl) row[sl] = row[L.S - 1];
+    return row;
+}
+
 // initial: a new problem (not an hsddp_advance step): QuadReference's clock restarts and every
 // phase's contact duration is read at its start time, as HKDProblem::initialization does
 // (get_contact_duration_at_t at t = 0 and at each phase end, HKDProblem.cpp:38,63)
@@ -439,20 +471,11 @@ static int build_refs(hsddp_handle h, const int *window_start, int window_len, c
         if (window_start[b] < 0 || window_start[b] >= h->ref_n) return fail(HSDDP_ERR_ARG, "window start outside the table");
     if (elem && phase_start_times)
         return fail(HSDDP_ERR_ARG, "per-element layouts: the phase start times follow each element's own float clock (NULL)");
-    // slot times as the reference forms them: t_offset (float, phase start relative to the first
-    // phase) + k dt (double), passed on as float (SinglePhase.cpp:243-287; set_time_offset,
-    // HKDProblem.cpp:103,208), snapped to a sample (QuadReference.cpp:60-76); per layout
+    // the phases' start times, per layout: the caller's, or the float clock's
     auto starts_of = [&](const Layout &L) {
+        if (!phase_start_times) return clock_starts(L, dt_sim);
         std::vector<float> start(L.P);
-        if (phase_start_times) {
-            for (int i = 0; i < L.P; ++i) start[i] = phase_start_times[i] - phase_start_times[0];
-        } else {  // the float clock of HKDProblem::initialization (t += dt_sim per knot)
-            float t = 0.0f;
-            for (int i = 0; i < L.P; ++i) {
-                start[i] = t;
-                for (int k = 0; k < L.N[i]; ++k) t += dt_sim;
-            }
-        }
+        for (int i = 0; i < L.P; ++i) start[i] = phase_start_times[i] - phase_start_times[0];
         return start;
     };
     const int sz = window_len - 1;
@@ -466,13 +489,7 @@ static int build_refs(hsddp_handle h, const int *window_start, int window_len, c
         auto it = keys.find(key);
         if (it == keys.end()) {
             const std::vector<float> start = starts_of(L);
-            std::vector<int> row(p.S, 0);
-            for (int i = 0; i < L.P; ++i)
-                for (int k = 0; k <= L.N[i]; ++k) {
-                    const float t = (float)((double)start[i] + k * (double)dt_sim);
-                    row[L.s0[i] + k] = sample_at(t, h->ref_dt, sz);
-                }
-            for (int sl = L.S; sl < p.S; ++sl) row[sl] = row[L.S - 1];
+            const std::vector<int> row = slot_samples(L, start, dt_sim, h->ref_dt, sz, p.S);
             it = keys.emplace(key, (int)map_starts.size()).first;
             idx.insert(idx.end(), row.begin(), row.end());
             map_starts.push_back(start);
@@ -500,6 +517,7 @@ static int build_refs(hsddp_handle h, const int *window_start, int window_len, c
     h->dt_sim = dt_sim;
     if (initial) {
         h->t_cur = 0;
+        h->t_el.clear();
         h->durations.assign((size_t)p.B * p.P * 4, 0.0);
         for (int b = 0; b < p.B; ++b) {
             const std::vector<float> &start = map_starts[elem ? map_id[b] : 0];
@@ -553,22 +571,24 @@ static int advance_impl(hsddp_handle h, int n_steps, float plan_duration, float 
     auto leq = [](float a, float b) { return a < b || std::abs(a - b) <= 1e-6f; };
     int adv = 0;  // samples per simulation step
     for (int i = 1; leq(i * dt, dts); ++i) adv++;
-    // QuadReference::step for every step: the window starts and the clock (shared by the batch)
+    // QuadReference::step for every step: the window starts and the clock (shared by the batch, or
+    // each element's own once hsddp_restart_elements has set some element's back to 0)
     const int P0 = p.P;  // stride of the current contact rows [B][P0 + 1][4] and durations [B][P0][4]
     std::vector<std::vector<int>> wsj(n_steps);  // window starts at each step
-    std::vector<float> relj(n_steps);            // new_end - new_start at each step
+    std::vector<std::vector<float>> relj(n_steps);  // new_end - new_start at each step, per clock
     std::vector<int> ws(h->win_start);
-    float t_cur = h->t_cur;
+    std::vector<float> t_cur(h->t_el.empty() ? std::vector<float>(1, h->t_cur) : h->t_el);
     for (int j = 0; j < n_steps; ++j) {
         for (int a = 0; a < adv; ++a) {
-            t_cur += dt;
+            for (float &t : t_cur) t += dt;
             for (int &w : ws) w++;
         }
         for (int &w : ws)
             if (w >= h->ref_n) return fail(HSDDP_ERR_ARG, "the reference window ran past the table");
         wsj[j] = ws;
-        relj[j] = (t_cur + plan_duration) - t_cur;  // new_end_time - new_start_time
+        for (float t : t_cur) relj[j].push_back((t + plan_duration) - t);  // new_end_time - new_start_time
     }
+    auto rel_at = [&](int b, int j) { return relj[j][relj[j].size() == 1 ? 0 : b]; };
     auto sample_w = [&](const std::vector<int> &w, int b, float t) -> const hsddp_quad_state & {
         const int k = w[Br == 1 ? 0 : b] + sample_at(t, dt, sz);
         return h->table_host[std::min(k, h->ref_n - 1)];
@@ -576,10 +596,10 @@ static int advance_impl(hsddp_handle h, int n_steps, float plan_duration, float 
     // a phase's sample: of an old phase its row of the handle's contacts / durations, of one these
     // steps start the table's at the horizon end of its first step
     auto phase_contact = [&](int b, const ShiftPhase &f) -> const int * {
-        return f.src >= 0 ? &h->contacts[((size_t)b * (P0 + 1) + f.src) * 4] : sample_w(wsj[f.born], b, relj[f.born]).contact;
+        return f.src >= 0 ? &h->contacts[((size_t)b * (P0 + 1) + f.src) * 4] : sample_w(wsj[f.born], b, rel_at(b, f.born)).contact;
     };
     auto phase_duration = [&](int b, const ShiftPhase &f) -> const double * {
-        return f.src >= 0 ? &h->durations[((size_t)b * P0 + f.src) * 4] : sample_w(wsj[f.born], b, relj[f.born]).status_dur;
+        return f.src >= 0 ? &h->durations[((size_t)b * P0 + f.src) * 4] : sample_w(wsj[f.born], b, rel_at(b, f.born)).status_dur;
     };
     // with the handle's shared layout and window, an element whose contact rows equal element 0's
     // steps exactly as element 0 does (the MPC batch of one gait): its bookkeeping is element 0's
@@ -614,7 +634,7 @@ static int advance_impl(hsddp_handle h, int n_steps, float plan_duration, float 
         W.flags.assign(n_steps, 0);
         for (int j = 0; j < n_steps; ++j) {
             if ((rc = st.drop_front("advance", why))) return fail(rc, why);
-            const int *nc = sample_w(wsj[j], b, relj[j]).contact, *lc = phase_contact(b, st.ph.back());
+            const int *nc = sample_w(wsj[j], b, rel_at(b, j)).contact, *lc = phase_contact(b, st.ph.back());
             int cc = 0;
             for (int l = 0; l < 4; ++l) cc |= nc[l] != lc[l];
             if ((rc = st.extend_back(cc, "advance", why))) return fail(rc, why);
@@ -666,7 +686,7 @@ static int advance_impl(hsddp_handle h, int n_steps, float plan_duration, float 
         for (int l = 0; l < 4; ++l)
             contacts[((size_t)b * (P + 1) + Pb) * 4 + l] =
                 W.next_kind == 0 ? h->contacts[((size_t)b * (P0 + 1) + W.P_old) * 4 + l]
-                : W.next_kind == 1 ? sample_w(wsj[W.next_step], b, relj[W.next_step]).contact[l]
+                : W.next_kind == 1 ? sample_w(wsj[W.next_step], b, rel_at(b, W.next_step)).contact[l]
                                    : sample_w(wsj[W.next_step], b, plan_duration + dt_mpc).contact[l];
     }
     stage(2);
@@ -679,7 +699,8 @@ static int advance_impl(hsddp_handle h, int n_steps, float plan_duration, float 
         h->contacts_current = true;
     }
     h->durations.swap(dur);
-    h->t_cur = t_cur;
+    if (h->t_el.empty()) h->t_cur = t_cur[0];
+    else h->t_el = t_cur;
     stage(4);
     if (timing)
         std::fprintf(stderr, "hsddp_advance us: bookkeeping %.1f shift %.1f contacts %.1f refs %.1f update %.1f\n",
@@ -717,6 +738,325 @@ extern "C" int hsddp_advance(hsddp_handle h, int n_steps, float plan_duration, f
     if (rc == HSDDP_OK) return overflow ? fail(HSDDP_ERR_UNSUPPORTED, msg) : HSDDP_OK;
     if (overflow) fail(rc, std::string(hsddp_last_error()) + " (and " + msg + ")");
     return rc;
+}
+
+// ---- single elements started again (HKDProblem::initialization for a subset) -------------------
+// The sweep pairs (Bufs::pairs: two elements of one layout per wave) after the listed elements of a
+// per-element handle took new layouts (hsddp_handle_t::lays), patched in place: a listed element
+// leaves its pair (its partner stays alone), the listed elements pair up among themselves by new
+// layout, emptied entries are filled from the end.  Only the entries that change go to the device.
+// (The next set_layouts — every shift of a per-element handle — pairs the whole batch afresh.)
+static int repair_pairs(hsddp_handle h, const std::vector<int> &list)
+{
+    std::vector<int> &pr = h->pairs_host, &of = h->pair_of;
+    int np = h->p.n_pairs;
+    std::vector<int> freed, touched;
+    for (int b : list) {
+        const int q = of[b], partner = pr[2 * q] == b ? pr[2 * q + 1] : pr[2 * q];
+        pr[2 * q] = partner;
+        pr[2 * q + 1] = -1;
+        if (partner < 0) freed.push_back(q);
+        else touched.push_back(q);
+        of[b] = -1;
+    }
+    std::map<std::vector<int>, std::vector<int>> groups;
+    for (int b : list) {
+        const Layout &L = h->lays[b];
+        std::vector<int> key(L.N, L.N + L.P);
+        key.push_back(-1);
+        key.insert(key.end(), L.ss, L.ss + L.P);
+        groups[key].push_back(b);
+    }
+    for (auto &g : groups)
+        for (size_t j = 0; j < g.second.size(); j += 2) {
+            int q;
+            if (!freed.empty()) { q = freed.back(); freed.pop_back(); }
+            else q = np++;
+            if ((size_t)2 * q + 1 >= pr.size()) pr.resize((size_t)2 * q + 2, -1);
+            pr[2 * q] = g.second[j];
+            pr[2 * q + 1] = j + 1 < g.second.size() ? g.second[j + 1] : -1;
+            of[pr[2 * q]] = q;
+            if (pr[2 * q + 1] >= 0) of[pr[2 * q + 1]] = q;
+            touched.push_back(q);
+        }
+    std::sort(freed.begin(), freed.end(), std::greater<int>());
+    for (int q : freed) {  // emptied entries: the last pair moves in
+        const int last = np - 1;
+        if (q != last) {
+            pr[2 * q] = pr[2 * last];
+            pr[2 * q + 1] = pr[2 * last + 1];
+            of[pr[2 * q]] = q;
+            if (pr[2 * q + 1] >= 0) of[pr[2 * q + 1]] = q;
+            touched.push_back(q);
+        }
+        --np;
+    }
+    if ((size_t)np > (size_t)h->p.B) return fail(HSDDP_ERR_ARG, "sweep pairs exceed the batch");
+    int rc;
+    for (int q : touched)
+        if (q < np && (rc = h2d((int *)h->d.pairs + 2 * q, &pr[2 * q], 2 * sizeof(int), h->stream))) return rc;
+    h->p.n_pairs = np;
+    return HSDDP_OK;
+}
+
+// The host side of hsddp_restart_elements: every listed element's window segmented anew
+// (plan_restart, hsddp_phases.cpp), its layout, contact rows, durations, window start and clock
+// replaced, and the device rows of a new problem written for the listed elements only
+// (hsddp_restart.hip).  The per-phase and per-slot buffers are strided by the batch's largest P and
+// S: when the restart changes either, the other elements' rows move to the new strides first, by
+// the shift's gather with identity slot maps (no step), and the references are rebuilt at the new
+// stride — one pass over the batch, as a shift is; otherwise nothing of another element is touched.
+// Every refusal comes before the first change to the handle.
+extern "C" int hsddp_restart_elements(hsddp_handle h, const int *mask, const int *window_start, float plan_duration,
+                                      float dt_mpc, const double *x0)
+{
+    if (!h || !mask || !window_start) return fail(HSDDP_ERR_ARG, "null argument");
+    if (!h->have_problem) return fail(HSDDP_ERR_ARG, "upload the problem first");
+    if (!h->ref_table || h->win_start.empty() || h->table_host.empty())
+        return fail(HSDDP_ERR_UNSUPPORTED, "references not built from a table (hsddp_set_reference_table + "
+                                           "hsddp_build_references)");
+    Params &p = h->p;
+    const int B = p.B, Br = h->Bref;
+    std::vector<int> list;
+    for (int b = 0; b < B; ++b)
+        if (mask[b]) list.push_back(b);
+    const int n = (int)list.size();
+    if (n == 0) return HSDDP_OK;  // nothing restarts: nothing is launched, nothing changes
+    const bool all = n == B;
+    if (!all && Br == 1)
+        return fail(HSDDP_ERR_UNSUPPORTED, "shared references: a restart of some elements needs per-element references "
+                                           "(ref_per_element = 1)");
+    if (!h->refs_on_device || !h->contacts_current || h->contacts.size() != (size_t)B * (p.P + 1) * 4 ||
+        h->durations.size() != (size_t)B * p.P * 4)
+        return fail(HSDDP_ERR_ARG, "no references and contacts of the current layout on the handle (after hsddp_shift: "
+                                   "hsddp_build_references and hsddp_update_problem first)");
+    std::vector<RestartPlan> plans(n);
+    std::string why;
+    for (int m = 0; m < n; ++m) {
+        if (Br == 1 && window_start[list[m]] != window_start[0])
+            return fail(HSDDP_ERR_UNSUPPORTED, "shared references hold one window: every window start must be the same");
+        if (int rc = plan_restart(h->table_host.data(), h->ref_n, window_start[list[m]], h->win_len, h->ref_dt,
+                                  plan_duration, h->dt_sim, dt_mpc, p.Kc, plans[m], why))
+            return fail(rc, why);
+    }
+    // The batch's largest P and S after the restart (the strides of the per-phase and per-slot
+    // buffers).  Unlisted elements keep theirs, so the old strides stand unless a new layout exceeds
+    // them or a listed element alone held them; only then is every element looked at.
+    const bool elem = !h->lays.empty();
+    int Pn = 0, Sn = 0;
+    bool held = false;  // a listed element's old layout has the batch's largest P or S
+    for (int m = 0; m < n; ++m) {
+        Pn = std::max(Pn, plans[m].L.P);
+        Sn = std::max(Sn, plans[m].L.S);
+        const Layout &Lo = layout_of(h, list[m]);
+        held = held || Lo.P == p.P || Lo.S == p.S;
+    }
+    if (!all) {
+        if (!elem || !held || (Pn >= p.P && Sn >= p.S)) {
+            Pn = std::max(Pn, p.P);
+            Sn = std::max(Sn, p.S);
+        } else {
+            std::vector<char> listed(B, 0);
+            for (int b : list) listed[b] = 1;
+            for (int b = 0; b < B; ++b)
+                if (!listed[b]) {
+                    Pn = std::max(Pn, h->lays[b].P);
+                    Sn = std::max(Sn, h->lays[b].S);
+                }
+        }
+    }
+    if ((size_t)Sn > h->S_cap) return fail(HSDDP_ERR_ARG, "restarted layout exceeds the handle's capacity");
+    // one layout for the batch stays (or becomes) the handle's shared one: every element restarted
+    // onto one layout, or some elements of a shared-layout handle restarted onto that layout with no
+    // phase of it at its end.  (Elements of a per-element handle that come to agree stay per element.)
+    bool one = true;
+    for (int m = 1; m < n && one; ++m) one = !std::memcmp(&plans[m].L, &plans[0].L, sizeof(Layout));
+    if (!all)
+        one = one && !elem && !std::memcmp(&plans[0].L, &h->shared, sizeof(Layout)) &&
+              std::all_of(h->reach_end.begin(), h->reach_end.end(), [](int r) { return r == 0; });
+    HIPCHK(hipSetDevice(h->desc.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const bool restride = Pn != p.P || Sn != p.S;
+    // in place: the strides stand and the handle has per-element layouts already, so the listed
+    // elements' layout records, sweep pairs and table rows are patched and nothing of size B is built
+    const bool in_place = elem && !restride && !all;
+    const int P0 = p.P;
+    int rc;
+    std::vector<Layout> lays;
+    std::vector<int> reach;
+    if (!in_place && !one) {  // every element's layout and reach flags after the restart
+        lays.resize(B);
+        reach.assign((size_t)B * HSDDP_MAX_PHASES, 0);
+        for (int b = 0; b < B; ++b) {
+            lays[b] = layout_of(h, b);
+            std::copy(reach_of(h, b), reach_of(h, b) + lays[b].P, &reach[(size_t)b * HSDDP_MAX_PHASES]);
+        }
+        for (int m = 0; m < n; ++m) {
+            lays[list[m]] = plans[m].L;
+            std::fill_n(&reach[(size_t)list[m] * HSDDP_MAX_PHASES], HSDDP_MAX_PHASES, 0);
+        }
+    }
+    if (restride) {
+        // the other elements' rows to the new strides: a shift of no steps (identity maps; the listed
+        // elements' rows come out zero and are written below)
+        ShiftPlan plan;
+        plan.map_id.assign(B, 0);
+        std::map<std::vector<int>, int> keys;
+        std::vector<int> listed(B, -1);
+        for (int m = 0; m < n; ++m) listed[list[m]] = m;
+        for (int b = 0; b < B; ++b) {
+            const Layout L = listed[b] >= 0 ? plans[listed[b]].L : layout_of(h, b);
+            std::vector<int> key = listed[b] >= 0 ? std::vector<int>(L.N, L.N + L.P) : shift_key(L, reach_of(h, b), 0, nullptr);
+            key.push_back(listed[b] >= 0 ? -2 : -3);
+            auto it = keys.find(key);
+            if (it == keys.end()) {
+                std::vector<ShiftPhase> ph;
+                if (listed[b] >= 0) {
+                    for (int i = 0; i < L.P; ++i) {
+                        ShiftPhase f;
+                        f.N = L.N[i]; f.ss = L.ss[i]; f.reach = 0;
+                        f.xs.assign(f.N + 1, -1); f.us.assign(f.N, -1); f.rs.assign(f.N, -1);
+                        ph.push_back(f);
+                    }
+                } else {
+                    ph = PhaseStepper(L, reach_of(h, b)).ph;
+                }
+                it = keys.emplace(std::move(key), (int)plan.phs.size()).first;
+                plan.phs.push_back(std::move(ph));
+                plan.nl.push_back(L);
+            }
+            plan.map_id[b] = it->second;
+        }
+        const bool pending = h->need_inputs;
+        if ((rc = shift_apply(h, plan, false, nullptr, false))) return rc;
+        h->need_inputs = pending;
+    }
+    // the layouts (a restriding shift_apply has installed the per-element ones)
+    if (one) {
+        const int none[HSDDP_MAX_PHASES] = {0};
+        adopt_shared_layout(h, plans[0].L, none);
+    } else if (in_place) {
+        for (int m = 0; m < n; ++m) {  // (the device records go with the restart's kernel)
+            h->lays[list[m]] = plans[m].L;
+            std::fill_n(&h->reach_el[(size_t)list[m] * HSDDP_MAX_PHASES], HSDDP_MAX_PHASES, 0);
+        }
+        if ((rc = repair_pairs(h, list))) return rc;
+    } else if (!restride) {
+        if ((rc = set_layouts(h, lays))) return rc;
+        h->reach_el = reach;
+    }
+    // contact rows [B][P + 1][4] and durations [B][P][4]: the listed elements' new; at a new stride
+    // the others' rows move
+    const int P = p.P;
+    if (restride) {
+        std::vector<int> contacts((size_t)B * (P + 1) * 4, 0);
+        std::vector<double> dur((size_t)B * P * 4, 0.0);
+        for (int b = 0; b < B; ++b) {
+            const int Pb = std::min(layout_of(h, b).P, P0);
+            std::copy_n(&h->contacts[(size_t)b * (P0 + 1) * 4], (Pb + 1) * 4, &contacts[(size_t)b * (P + 1) * 4]);
+            std::copy_n(&h->durations[(size_t)b * P0 * 4], Pb * 4, &dur[(size_t)b * P * 4]);
+        }
+        h->contacts.swap(contacts);
+        h->durations.swap(dur);
+    }
+    std::vector<int> rows((size_t)n * (P + 1) * 4, 0);  // the listed elements' rows, compacted
+    for (int m = 0; m < n; ++m) {
+        const int b = list[m], Pb = plans[m].L.P;
+        std::fill_n(&h->contacts[(size_t)b * (P + 1) * 4], (P + 1) * 4, 0);
+        std::fill_n(&h->durations[(size_t)b * P * 4], P * 4, 0.0);
+        std::copy_n(plans[m].contacts, (Pb + 1) * 4, &h->contacts[(size_t)b * (P + 1) * 4]);
+        std::copy_n(plans[m].durations, Pb * 4, &h->durations[(size_t)b * P * 4]);
+        std::copy_n(plans[m].contacts, (Pb + 1) * 4, &rows[(size_t)m * (P + 1) * 4]);
+    }
+    h->contacts_current = true;
+    if (restride && (rc = h2d((void *)h->d.contacts, h->contacts.data(), h->contacts.size() * sizeof(int), h->stream)))
+        return rc;
+    // the window starts; references: at a new stride every element's are rebuilt; shared ones (every
+    // element restarts) are built as a whole; else the kernel forms the listed elements' own
+    for (int m = 0; m < n; ++m) h->win_start[Br == 1 ? 0 : list[m]] = window_start[list[m]];
+    if (restride || Br == 1) {
+        const std::vector<int> ws(h->win_start);
+        if ((rc = build_refs(h, ws.data(), h->win_len, nullptr, h->dt_sim, false))) return rc;
+    }
+    // the clocks: QuadReference's t_cur restarts for the listed elements
+    if (all) {
+        h->t_cur = 0;
+        h->t_el.clear();
+    } else {
+        if (h->t_el.empty()) h->t_el.assign(B, h->t_cur);
+        for (int b : list) h->t_el[b] = 0;
+    }
+    // the device rows: list, window starts, slot maps (one per distinct new layout), contact rows, x0
+    const int sz = h->win_len - 1;
+    std::map<std::vector<int>, int> maps;
+    std::vector<int> idx, map_id(n), start(n);
+    for (int m = 0; m < n; ++m) {
+        const Layout &L = plans[m].L;
+        std::vector<int> key(L.N, L.N + L.P);
+        auto it = maps.find(key);
+        if (it == maps.end()) {
+            const std::vector<int> row = slot_samples(L, clock_starts(L, h->dt_sim), h->dt_sim, h->ref_dt, sz, p.S);
+            it = maps.emplace(std::move(key), (int)maps.size()).first;
+            idx.insert(idx.end(), row.begin(), row.end());
+        }
+        map_id[m] = it->second;
+        start[m] = window_start[list[m]];
+    }
+    std::vector<Layout> recs;  // the listed elements' layout records (in place: written by the kernel)
+    if (in_place)
+        for (int m = 0; m < n; ++m) recs.push_back(plans[m].L);
+    const size_t nl = recs.size() * (sizeof(Layout) / sizeof(int));
+    const size_t ni = (size_t)3 * n + idx.size() + rows.size() + nl, ib = (ni * sizeof(int) + 255) & ~(size_t)255;
+    char *buf;
+    if ((rc = scratch(h, ib + (x0 ? (size_t)n * NX * sizeof(double) : 0), &buf))) return rc;
+    int *dl = (int *)buf, *ds = dl + n, *dm = ds + n, *di = dm + n, *dc = di + idx.size(), *dr = dc + rows.size();
+    double *dx = (double *)(buf + ib);
+    std::vector<double> xs;
+    if (x0) {
+        xs.resize((size_t)n * NX);
+        for (int m = 0; m < n; ++m) std::copy_n(x0 + (size_t)list[m] * NX, NX, &xs[(size_t)m * NX]);
+    }
+    if ((rc = h2d(dl, list.data(), n * sizeof(int), h->stream)) || (rc = h2d(ds, start.data(), n * sizeof(int), h->stream)) ||
+        (rc = h2d(dm, map_id.data(), n * sizeof(int), h->stream)) ||
+        (rc = h2d(di, idx.data(), idx.size() * sizeof(int), h->stream)) ||
+        (rc = h2d(dc, rows.data(), rows.size() * sizeof(int), h->stream)) ||
+        (nl && (rc = h2d(dr, recs.data(), nl * sizeof(int), h->stream))) ||
+        (x0 && (rc = h2d(dx, xs.data(), xs.size() * sizeof(double), h->stream))))
+        return rc;
+    RestartArgs a{};
+    a.n = n; a.list = dl; a.start = ds; a.map_id = dm; a.slot_idx = di; a.contacts = dc;
+    a.x0 = x0 ? dx : nullptr;
+    a.table = h->ref_table; a.table_n = h->ref_n;
+    a.build_refs = Br == 1 ? 0 : 1;
+    a.lay = nl ? (const Layout *)dr : nullptr;
+    // HSDDP_RESTART_TIMING=1: the kernels' device time (HIP events) to stderr (a diagnostic)
+    static const bool timing = std::getenv("HSDDP_RESTART_TIMING") != nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (timing) {
+        HIPCHK(hipEventCreate(&ev[0]));
+        HIPCHK(hipEventCreate(&ev[1]));
+        HIPCHK(hipEventRecord(ev[0], h->stream));
+    }
+    launch_restart(p, h->d, a, h->stream);
+    HIPCHK(hipGetLastError());
+    if (timing) HIPCHK(hipEventRecord(ev[1], h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));  // (the pageable host rows above are read until here)
+    if (timing) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        hipEventDestroy(ev[0]);
+        hipEventDestroy(ev[1]);
+        std::fprintf(stderr, "hsddp_restart_elements kernels ms: %.4f (B %d, restarted %d%s)\n", ms, B, n,
+                     in_place ? ", in place" : restride ? ", new strides" : "");
+    }
+    // what the handle caches of rows and layouts: the slot costs are recomputed by the next k_lq, a
+    // simulation held and this tick's measured foot placements are of the old problems; the
+    // iteration graphs are keyed on Params / Bufs and re-captured when the layouts changed them
+    h->slots_fresh = false;
+    h->sim_fresh = false;
+    h->meas_held = false;
+    if (!x0) h->need_inputs = true;  // as hsddp_advance with x0 = NULL leaves them
+    return HSDDP_OK;
 }
 
 extern "C" int hsddp_get_phase_info(hsddp_handle h, int *contacts, double *durations)

@@ -143,7 +143,18 @@ struct ElemState {
     int done, inner_done, ls_active, accepted, status, iters, outer_iters, n_ls;
     int hist_n;  // entries pushed to the solver-info history (MultiPhaseDDP.cpp:277-280, 368-371)
     int ovr, td_stale;  // (above; persistent across solves)
+    int inner_n;  // line searches finished in the current outer iteration (per-element budgets)
 };
+static_assert(sizeof(ElemState) == 160, "ElemState: 14 doubles and 12 ints, no padding left");
+
+// Per-element iteration budgets (hsddp_set_element_budgets): budget [B][2] = (max_AL_iter,
+// max_DDP_iter) of each element on the device, or null: the handle-wide options, enforced by the
+// host's loop bounds alone.  With budgets the host loops to the largest and an element past its own
+// bound is inert as one whose early-exit test fired: ElemState::done once its max_AL_iter outer
+// iterations have ended (k_outer_end, after its AL update; k_outer_begin for a budget of 0),
+// ElemState::inner_done once it has finished max_DDP_iter line searches in the outer iteration
+// (k_decide; k_outer_begin for a budget of 0).  Every kernel honours the two flags with and without
+// no_early_exit, which only keeps the convergence tests from setting them.
 
 struct Bufs {
     const int *contacts;                   // [B][P+1][4]
@@ -201,8 +212,10 @@ struct Bufs {
 // kernel launchers (hsddp_kernels.hip)
 // tix: the trial's index in the inner iteration's line search (-1: the initial rollout)
 // (last: this trial is the search's last step size — used when the rollout launch also decides)
-void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int init, int tix, hipStream_t st);
-void launch_decide(const Params &p, const Bufs &d, double eps, int last, int init, int tix, hipStream_t st);
+void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
+                    hipStream_t st);
+void launch_decide(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
+                   hipStream_t st);
 // nominal rows of every element into buffer 0 (Bufs::sel bit 0 cleared), for host transfers
 void launch_normalize(const Params &p, const Bufs &d, hipStream_t st);
 // every element's working rows back at its nominal ones (sel), its Defect rows zero
@@ -210,9 +223,9 @@ void launch_reset_working(const Params &p, const Bufs &d, hipStream_t st);
 void launch_lq(const Params &p, const Bufs &d, hipStream_t st);
 void launch_riccati(const Params &p, const Bufs &d, hipStream_t st);
 void launch_lin_rollout(const Params &p, const Bufs &d, hipStream_t st);
-void launch_outer_begin(const Params &p, const Bufs &d, hipStream_t st);
+void launch_outer_begin(const Params &p, const Bufs &d, const int *budget, hipStream_t st);
 void launch_reb_update(const Params &p, const Bufs &d, hipStream_t st);
-void launch_outer_end(const Params &p, const Bufs &d, hipStream_t st);
+void launch_outer_end(const Params &p, const Bufs &d, const int *budget, hipStream_t st);
 void launch_reset_elements(const Params &p, const Bufs &d, hipStream_t st);
 void launch_init_params(const Params &p, const Bufs &d, hipStream_t st);
 // TD_PENDING touchdown masks resolved from the contact rows (after new contacts are uploaded)

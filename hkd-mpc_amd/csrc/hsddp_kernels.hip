@@ -1135,7 +1135,8 @@ DEV void diverged_fixup(const Params &p, const Bufs &d, const LayT<EL> &L, int b
 // mixed ones (diverged_fixup); max_tconstr / max_pconstr then cover the phases before the break
 // only (MultiPhaseDDP.cpp:83-92).
 template <bool EL>
-DEV void decide_group(const Params &p, const Bufs &d, double eps, int last, int init, int tix, int group)
+DEV void decide_group(const Params &p, const Bufs &d, double eps, int last, int init, int tix, int group,
+                      const int *budget)
 {
     const int lane = threadIdx.x, g = lane & 15, base = lane & ~15;
     const int b = group * 4 + (lane >> 4);
@@ -1251,16 +1252,19 @@ DEV void decide_group(const Params &p, const Bufs &d, double eps, int last, int 
             E.inner_done = 1;
         else
             push_info();
+        // the element's own inner bound (MultiPhaseDDP.cpp:304): its last iteration of this outer one
+        E.inner_n += 1;
+        if (budget && E.inner_n >= budget[2 * b + 1]) E.inner_done = 1;
     }
 }
 
 // (six waves per SIMD as before the divergence path: that rare path spills instead)
 template <bool EL>
 __global__ __launch_bounds__(64) void k_decide(Params p, Bufs d, double eps, int last,
-                                                                                         int init, int tix)
+                                                                                         int init, int tix, const int *budget)
 {
     if (ls_skip(d, tix)) return;
-    decide_group<EL>(p, d, eps, last, init, tix, blockIdx.x);
+    decide_group<EL>(p, d, eps, last, init, tix, blockIdx.x, budget);
 }
 
 // One line-search trial: the slot and boundary blocks (rollout_block), and — FUSE, small batches
@@ -1270,7 +1274,7 @@ __global__ __launch_bounds__(64) void k_decide(Params p, Bufs d, double eps, int
 // and resets the ticket counter.  One launch less per trial on the latency path of C1.
 template <bool EL, bool FUSE, bool WIDE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HSDDP_ROLLOUT_WAVES))) void k_rollout(
-    Params p, Bufs d, double eps, int init, int tix, int last)
+    Params p, Bufs d, double eps, int init, int tix, int last, const int *budget)
 {
     if (ls_skip(d, tix)) return;
     rollout_block<EL, WIDE>(p, d, eps, init, tix);
@@ -1281,7 +1285,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HSDDP_ROLLOU
         __syncthreads();
         if (ticket != (int)gridDim.x - 1) return;
         __threadfence();
-        for (int q = 0; q < (p.B + 3) / 4; ++q) decide_group<EL>(p, d, eps, last, init, tix, q);
+        for (int q = 0; q < (p.B + 3) / 4; ++q) decide_group<EL>(p, d, eps, last, init, tix, q, budget);
         if (threadIdx.x == 0) d.counter[7] = 0;
     }
 }
@@ -1337,17 +1341,20 @@ __global__ void k_reset_sel(Params p, Bufs d)
     if (b < p.B) d.sel[b] = sel_code(nom_buf(d, b), nom_buf(d, b));
 }
 
-__global__ void k_outer_begin(Params p, Bufs d)
+__global__ void k_outer_begin(Params p, Bufs d, const int *budget)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= p.B) return;
     ElemState &E = d.el[b];
     if (E.done) return;
+    // the element's own outer bound (MultiPhaseDDP.cpp:257): no outer iteration at all
+    if (budget && E.outer_iters >= budget[2 * b]) { E.done = 1; return; }
     E.outer_iters += 1;
     E.max_t_prev = E.max_t;
     E.max_p_prev = E.max_p;
     E.reg = 0.0;
-    E.inner_done = 0;
+    E.inner_done = (budget && budget[2 * b + 1] <= 0) ? 1 : 0;  // (an inner bound of 0: no iteration)
+    E.inner_n = 0;
 }
 
 // update_REB_params (ConstraintsBase.h:168-183) per (element, control slot)
@@ -1385,7 +1392,7 @@ __global__ __launch_bounds__(256) void k_reb_update(Params p, Bufs d)
 
 // update_AL_params (ConstraintsBase.h:349-365) + outer convergence tests (MultiPhaseDDP.cpp:397-408)
 template <bool EL>
-__global__ void k_outer_end(Params p, Bufs d)
+__global__ void k_outer_end(Params p, Bufs d, const int *budget)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= p.B) return;
@@ -1413,6 +1420,8 @@ __global__ void k_outer_end(Params p, Bufs d)
                 }
             }
     }
+    // the element's own outer bound: that was its last outer iteration (its AL / ReB update done)
+    if (budget && E.outer_iters >= budget[2 * b]) E.done = 1;
     if (p.no_early_exit) return;
     if (E.max_t < p.tconstr_thresh && fabs(E.max_p) < p.pconstr_thresh && E.feas <= p.feas_thresh) E.done = 1;
     else if (fabs(E.max_t - E.max_t_prev) < 0.0001 && fabs(E.max_p - E.max_p_prev) < 0.0001 &&
@@ -1774,7 +1783,8 @@ static bool fused_decide(const Params &p)
     return !(e && *e && *e != '0');
 }
 
-void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int init, int tix, hipStream_t st)
+void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
+                    hipStream_t st)
 {
     if (p.ms0) {  // single shooting: every knot simulated (k_rollout_ss)
         LAUNCH_EL(k_rollout_ss, dim3((p.B + 3) / 4), dim3(64), st, p, d, eps, init, tix);
@@ -1785,27 +1795,28 @@ void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int in
     const bool wide = p.S >= RW;  // (rollout_block)
     if (fused_decide(p)) {
         if (p.elem_layout) {
-            if (wide) hipLaunchKernelGGL((k_rollout<true, true, true>), g, dim3(64), 0, st, p, d, eps, init, tix, last);
-            else hipLaunchKernelGGL((k_rollout<true, true, false>), g, dim3(64), 0, st, p, d, eps, init, tix, last);
+            if (wide) hipLaunchKernelGGL((k_rollout<true, true, true>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
+            else hipLaunchKernelGGL((k_rollout<true, true, false>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
         } else {
-            if (wide) hipLaunchKernelGGL((k_rollout<false, true, true>), g, dim3(64), 0, st, p, d, eps, init, tix, last);
-            else hipLaunchKernelGGL((k_rollout<false, true, false>), g, dim3(64), 0, st, p, d, eps, init, tix, last);
+            if (wide) hipLaunchKernelGGL((k_rollout<false, true, true>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
+            else hipLaunchKernelGGL((k_rollout<false, true, false>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
         }
         return;
     }
     if (p.elem_layout) {
-        if (wide) hipLaunchKernelGGL((k_rollout<true, false, true>), g, dim3(64), 0, st, p, d, eps, init, tix, last);
-        else hipLaunchKernelGGL((k_rollout<true, false, false>), g, dim3(64), 0, st, p, d, eps, init, tix, last);
+        if (wide) hipLaunchKernelGGL((k_rollout<true, false, true>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
+        else hipLaunchKernelGGL((k_rollout<true, false, false>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
     } else {
-        if (wide) hipLaunchKernelGGL((k_rollout<false, false, true>), g, dim3(64), 0, st, p, d, eps, init, tix, last);
-        else hipLaunchKernelGGL((k_rollout<false, false, false>), g, dim3(64), 0, st, p, d, eps, init, tix, last);
+        if (wide) hipLaunchKernelGGL((k_rollout<false, false, true>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
+        else hipLaunchKernelGGL((k_rollout<false, false, false>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
     }
     if (p.has_tail) LAUNCH_EL(k_rollout_tail, dim3((p.B + 63) / 64), dim3(64), st, p, d, eps, init, tix);
 }
-void launch_decide(const Params &p, const Bufs &d, double eps, int last, int init, int tix, hipStream_t st)
+void launch_decide(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
+                   hipStream_t st)
 {
     if (fused_decide(p)) return;  // decided by the rollout launch
-    LAUNCH_EL(k_decide, dim3((p.B + 3) / 4), dim3(64), st, p, d, eps, last, init, tix);
+    LAUNCH_EL(k_decide, dim3((p.B + 3) / 4), dim3(64), st, p, d, eps, last, init, tix, budget);
 }
 void launch_normalize(const Params &p, const Bufs &d, hipStream_t st)
 {
@@ -1872,17 +1883,17 @@ void launch_reset_working(const Params &p, const Bufs &d, hipStream_t st)
     hipLaunchKernelGGL(k_reset_defect, dim3(blocks_for((long)p.B * p.S * (NX / 2), 256)), dim3(256), 0, st, p, d);
     hipLaunchKernelGGL(k_reset_sel, dim3(blocks_for(p.B, 256)), dim3(256), 0, st, p, d);
 }
-void launch_outer_begin(const Params &p, const Bufs &d, hipStream_t st)
+void launch_outer_begin(const Params &p, const Bufs &d, const int *budget, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_outer_begin, dim3(blocks_for(p.B, 256)), dim3(256), 0, st, p, d);
+    hipLaunchKernelGGL(k_outer_begin, dim3(blocks_for(p.B, 256)), dim3(256), 0, st, p, d, budget);
 }
 void launch_reb_update(const Params &p, const Bufs &d, hipStream_t st)
 {
     LAUNCH_EL(k_reb_update, dim3(blocks_for((long)p.B * p.Kc, 256)), dim3(256), st, p, d);
 }
-void launch_outer_end(const Params &p, const Bufs &d, hipStream_t st)
+void launch_outer_end(const Params &p, const Bufs &d, const int *budget, hipStream_t st)
 {
-    LAUNCH_EL(k_outer_end, dim3(blocks_for(p.B, 256)), dim3(256), st, p, d);
+    LAUNCH_EL(k_outer_end, dim3(blocks_for(p.B, 256)), dim3(256), st, p, d, budget);
 }
 void launch_reset_elements(const Params &p, const Bufs &d, hipStream_t st)
 {

@@ -2,6 +2,7 @@
 #include "hsddp_phases.h"
 
 #include <cmath>
+#include <cstring>
 
 #include "../../include/hsddp.h"
 
@@ -106,6 +107,73 @@ int sample_at(float t, float dt, int sz)
     int k = (int)std::floor(t / dt);
     if (t - k * dt > 0.5 * dt) k++;
     return k > sz ? sz : k;
+}
+
+namespace {
+// approx_eq_scalar / approx_leq_scalar / approx_geq_scalar (HSDDP_Utils.h:46-78)
+bool approx_eq(float a, float b) { return std::abs(a - b) <= 1e-6f; }
+bool approx_leq(float a, float b) { return a < b || approx_eq(a, b); }
+bool approx_geq(float a, float b) { return a > b || approx_eq(a, b); }
+}  // namespace
+
+int segment_window(const hsddp_quad_state *w, int n_window, float dt_ref, float plan_duration, float dt_sim,
+                   float dt_mpc, hsddp_phase_plan *plan, std::string &why)
+{
+    if (!w || !plan || n_window < 1) { why = "null argument / empty window"; return HSDDP_ERR_ARG; }
+    if (!(dt_ref > 0) || !(dt_sim > 0)) { why = "dt_ref and dt_sim must be > 0"; return HSDDP_ERR_ARG; }
+    const int sz = n_window - 1;
+    std::memset(plan, 0, sizeof *plan);
+    int prev[4], cur[4];
+    double dur[4];
+    auto contact = [&](int *c, float t) { std::memcpy(c, w[sample_at(t, dt_ref, sz)].contact, 4 * sizeof(int)); };
+    auto duration = [&](double *d, float t) { std::memcpy(d, w[sample_at(t, dt_ref, sz)].status_dur, 4 * sizeof(double)); };
+    float t = 0.0f, start = 0.0f;
+    contact(prev, t);
+    duration(dur, t);
+    int P = 0;
+    while (approx_leq(t, plan_duration)) {
+        contact(cur, t);
+        const bool change = std::memcmp(cur, prev, sizeof cur) != 0;
+        if (change || approx_geq(t, plan_duration)) {
+            if (P >= HSDDP_MAX_PHASES) { why = "more than HSDDP_MAX_PHASES phases"; return HSDDP_ERR_ARG; }
+            const float end = t;
+            plan->start_times[P] = start;
+            plan->end_times[P] = end;
+            plan->horizons[P] = (int)std::round((end - start) / dt_sim);
+            std::memcpy(plan->contacts[P], prev, sizeof prev);
+            std::memcpy(plan->durations[P], dur, sizeof dur);
+            ++P;
+            std::memcpy(prev, cur, sizeof cur);
+            duration(dur, t);
+            start = end;
+        }
+        t += dt_sim;
+    }
+    plan->n_phases = P;
+    // the last phase's next contact (add_tconstr_one_phase, HKDProblem.cpp:272-276)
+    contact(plan->contacts[P], plan_duration + dt_mpc);
+    for (int i = 0; i < P; ++i)
+        if (plan->horizons[i] < 1) { why = "a phase of zero knots (dt_sim too coarse)"; return HSDDP_ERR_ARG; }
+    return HSDDP_OK;
+}
+
+int plan_restart(const hsddp_quad_state *table, int n_table, int start, int win_len, float dt_ref,
+                 float plan_duration, float dt_sim, float dt_mpc, int Kc, RestartPlan &out, std::string &why)
+{
+    if (!table || start < 0 || start >= n_table) { why = "window start outside the table"; return HSDDP_ERR_ARG; }
+    if (win_len < 1) { why = "empty reference window"; return HSDDP_ERR_ARG; }
+    hsddp_phase_plan plan;
+    const int n_window = win_len < n_table - start ? win_len : n_table - start;
+    if (int rc = segment_window(table + start, n_window, dt_ref, plan_duration, dt_sim, dt_mpc, &plan, why)) return rc;
+    if (plan.n_phases < 1) { why = "the window holds no phase"; return HSDDP_ERR_ARG; }
+    out = RestartPlan{};
+    if (int rc = build_layout(plan.n_phases, plan.horizons, nullptr, out.L, why)) return rc;
+    if (control_slots(out.L) != Kc) { why = "the restarted window's horizons must sum to the handle's Kc"; return HSDDP_ERR_ARG; }
+    for (int i = 0; i <= plan.n_phases; ++i)
+        for (int l = 0; l < 4; ++l) out.contacts[i * 4 + l] = plan.contacts[i][l];
+    for (int i = 0; i < plan.n_phases; ++i)
+        for (int l = 0; l < 4; ++l) out.durations[i * 4 + l] = plan.durations[i][l];
+    return HSDDP_OK;
 }
 
 }  // namespace hsddp

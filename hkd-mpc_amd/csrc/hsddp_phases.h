@@ -1,11 +1,16 @@
 // hsddp_phases.h — the phase bookkeeping of the batched HS-DDP solver on the host: the layout of
-// one element's phases, HKDProblem::update's edits of it (HKDProblem.cpp:117-222) and
-// QuadReference's sample rounding.  No HIP header, no handle and no global state: a plain C++
-// compiler builds hsddp_phases.cpp on its own (tests/drivers/phases_check.cpp).
+// one element's phases, HKDProblem::update's edits of it (HKDProblem.cpp:117-222),
+// HKDProblem::initialization's segmentation of a reference window (:15-68; hsddp_plan_phases and
+// the restart of single elements, hsddp_restart_elements) and QuadReference's sample rounding.  No
+// HIP header, no handle and no global state: a plain C++ compiler builds hsddp_phases.cpp on its
+// own (tests/drivers/phases_check.cpp, restart_check.cpp).
 #pragma once
 
 #include <string>
 #include <vector>
+
+struct hsddp_quad_state;
+struct hsddp_phase_plan;
 
 namespace hsddp {
 
@@ -55,6 +60,26 @@ struct PhaseStepper {
     // update_SS_config (HKDProblem.cpp:203-217), and the layout of the phases as they stand
     int finish(Layout &L, std::string &why);
 };
+
+// HKDProblem::initialization's segmentation (HKDProblem.cpp:15-68) of a window of n_window
+// samples into `plan` (hsddp_plan_phases, include/hsddp.h), with the reference's float clock.
+// A refusal returns its code with the text in `why`.
+int segment_window(const hsddp_quad_state *w, int n_window, float dt_ref, float plan_duration, float dt_sim,
+                   float dt_mpc, hsddp_phase_plan *plan, std::string &why);
+
+// One element's problem started again (hsddp_restart_elements): the segmentation of the window of
+// win_len samples at table[start] (clipped at the table's end), as a layout whose every state is a
+// shooting state (update_SS_config(N + 1), HKDProblem.cpp:104), its contact rows 0 .. P (row P:
+// the contact at plan_duration + dt_mpc) and its phases' contact durations.  No phase has reached
+// its end (quirk A15) and the element's clock restarts at 0.  Refused: a start outside the table,
+// and a plan whose horizons do not sum to the handle's Kc control slots.
+struct RestartPlan {
+    Layout L;
+    int contacts[(MAXP + 1) * 4];
+    double durations[MAXP * 4];
+};
+int plan_restart(const hsddp_quad_state *table, int n_table, int start, int win_len, float dt_ref,
+                 float plan_duration, float dt_sim, float dt_mpc, int Kc, RestartPlan &out, std::string &why);
 
 // sample index of relative time t in a window of sz + 1 samples (QuadReference.cpp:64-75, 81-91):
 // left-clipped, moved right when past the half step, clamped to the window end

@@ -1,8 +1,9 @@
 // hsddp_reference.cpp — host side of the batched reference construction:
 // the quad_reference.csv reader (QuadReference::load_top_level_data, Reference/QuadReference.cpp:
 // 129-290) and the phase segmentation of HKDProblem::initialization (HKDMPC/HKD-TrajOpt/
-// HKDProblem.cpp:15-68), both with the reference's float arithmetic.  The per-slot reference
-// tensors themselves are built on the device (hsddp_mpc.hip, k_build_refs).
+// HKDProblem.cpp:15-68; the routine itself is hsddp_phases.cpp's segment_window), both with the
+// reference's float arithmetic.  The per-slot reference tensors themselves are built on the device
+// (hsddp_mpc.hip, k_build_refs).
 #include <cmath>
 #include <cstring>
 #include <fstream>
@@ -13,8 +14,6 @@
 #include "hsddp_phases.h"
 
 extern "C" int hsddp_ref_fail(int code, const char *msg);  // hsddp_api.cpp: sets hsddp_last_error
-
-using hsddp::sample_at;  // (QuadReference's sample rounding)
 
 namespace {
 
@@ -69,11 +68,6 @@ void reorder(hsddp_quad_state &q)
         q.torque[3 * l + 2] = -q.torque[3 * l + 2];
     }
 }
-
-// approx_eq_scalar / approx_leq_scalar / approx_geq_scalar (HSDDP_Utils.h:46-78)
-bool approx_eq(float a, float b) { return std::abs(a - b) <= 1e-6f; }
-bool approx_leq(float a, float b) { return a < b || approx_eq(a, b); }
-bool approx_geq(float a, float b) { return a > b || approx_eq(a, b); }
 
 }  // namespace
 
@@ -139,40 +133,8 @@ extern "C" int hsddp_load_quad_reference(const char *path, int reorder_legs, flo
 extern "C" int hsddp_plan_phases(const hsddp_quad_state *w, int n_window, float dt_ref, float plan_duration,
                                  float dt_sim, float dt_mpc, hsddp_phase_plan *plan)
 {
-    if (!w || !plan || n_window < 1) return hsddp_ref_fail(HSDDP_ERR_ARG, "null argument / empty window");
-    if (!(dt_ref > 0) || !(dt_sim > 0)) return hsddp_ref_fail(HSDDP_ERR_ARG, "dt_ref and dt_sim must be > 0");
-    const int sz = n_window - 1;
-    std::memset(plan, 0, sizeof *plan);
-    int prev[4], cur[4];
-    double dur[4];
-    auto contact = [&](int *c, float t) { std::memcpy(c, w[sample_at(t, dt_ref, sz)].contact, 4 * sizeof(int)); };
-    auto duration = [&](double *d, float t) { std::memcpy(d, w[sample_at(t, dt_ref, sz)].status_dur, 4 * sizeof(double)); };
-    float t = 0.0f, start = 0.0f;
-    contact(prev, t);
-    duration(dur, t);
-    int P = 0;
-    while (approx_leq(t, plan_duration)) {
-        contact(cur, t);
-        const bool change = std::memcmp(cur, prev, sizeof cur) != 0;
-        if (change || approx_geq(t, plan_duration)) {
-            if (P >= HSDDP_MAX_PHASES) return hsddp_ref_fail(HSDDP_ERR_ARG, "more than HSDDP_MAX_PHASES phases");
-            const float end = t;
-            plan->start_times[P] = start;
-            plan->end_times[P] = end;
-            plan->horizons[P] = (int)std::round((end - start) / dt_sim);
-            std::memcpy(plan->contacts[P], prev, sizeof prev);
-            std::memcpy(plan->durations[P], dur, sizeof dur);
-            ++P;
-            std::memcpy(prev, cur, sizeof cur);
-            duration(dur, t);
-            start = end;
-        }
-        t += dt_sim;
-    }
-    plan->n_phases = P;
-    // the last phase's next contact (add_tconstr_one_phase, HKDProblem.cpp:272-276)
-    contact(plan->contacts[P], plan_duration + dt_mpc);
-    for (int i = 0; i < P; ++i)
-        if (plan->horizons[i] < 1) return hsddp_ref_fail(HSDDP_ERR_ARG, "a phase of zero knots (dt_sim too coarse)");
-    return HSDDP_OK;
+    // (the segmentation itself: hsddp_phases.cpp, shared with hsddp_restart_elements)
+    std::string why;
+    const int rc = hsddp::segment_window(w, n_window, dt_ref, plan_duration, dt_sim, dt_mpc, plan, why);
+    return rc ? hsddp_ref_fail(rc, why.c_str()) : HSDDP_OK;
 }

@@ -113,8 +113,8 @@ static void begin_launches(hsddp_handle h)
     if (h->p.trace) hipMemsetAsync(h->d.dbg, 0, (size_t)h->p.B * 16 * sizeof(unsigned long long), h->stream);
     sync_ref_columns(h);
     launch_reset_elements(h->p, h->d, h->stream);
-    launch_rollout(h->p, h->d, 0.0, 0, 1, -1, h->stream);
-    launch_decide(h->p, h->d, 0.0, 0, 1, -1, h->stream);
+    launch_rollout(h->p, h->d, 0.0, 0, 1, -1, budget_of(h), h->stream);
+    launch_decide(h->p, h->d, 0.0, 0, 1, -1, budget_of(h), h->stream);
     h->slots_fresh = true;
 }
 
@@ -144,8 +144,8 @@ static void iteration_launches(hsddp_handle h, const std::vector<double> &trials
     }
     tm.begin(2, e0);
     for (size_t t = 0; t < trials.size(); ++t) {
-        launch_rollout(p, d, trials[t], t + 1 == trials.size(), 0, (int)t, st);
-        launch_decide(p, d, trials[t], t + 1 == trials.size(), 0, (int)t, st);
+        launch_rollout(p, d, trials[t], t + 1 == trials.size(), 0, (int)t, budget_of(h), st);
+        launch_decide(p, d, trials[t], t + 1 == trials.size(), 0, (int)t, budget_of(h), st);
     }
     tm.end(2, e0);
     h->slots_fresh = true;
@@ -171,7 +171,7 @@ static int graph_launch(hsddp_handle h, const std::vector<double> &trials, int p
     hsddp_handle_t::IterGraph *hit = nullptr;
     for (auto &c : h->iter_graph)
         if (c.exec && c.par == par && !std::memcmp(&c.p, &pl, sizeof(Params)) &&
-            !std::memcmp(&c.d, &h->d, sizeof(Bufs)) && c.alpha == h->opt.alpha)
+            !std::memcmp(&c.d, &h->d, sizeof(Bufs)) && c.alpha == h->opt.alpha && c.budget == budget_of(h))
             hit = &c;
     if (!hit) {
         auto &g = h->iter_graph[h->iter_graph_next];
@@ -201,6 +201,7 @@ static int graph_launch(hsddp_handle h, const std::vector<double> &trials, int p
         std::memcpy(&g.p, &pl, sizeof(Params));
         std::memcpy(&g.d, &h->d, sizeof(Bufs));
         g.alpha = h->opt.alpha;
+        g.budget = budget_of(h);
         g.par = par;
         hit = &g;
     }
@@ -228,7 +229,7 @@ static void outer_end_launches(hsddp_handle h, Timer &tm)
         h->reb_at_init = false;
     }
     if (h->opt.ReB_active) launch_reb_update(h->p, h->d, h->stream);
-    launch_outer_end(h->p, h->d, h->stream);
+    launch_outer_end(h->p, h->d, budget_of(h), h->stream);
     tm.end(3, e0);
 }
 
@@ -285,11 +286,13 @@ extern "C" int hsddp_solve(hsddp_handle h, hsddp_stats *stats)
     int iters = 0, outers = 0, nbwd = 0;
     const bool checks = !h->opt.no_early_exit;
     const bool graph = checks && graphs_enabled();
-    for (int ou = 0; ou < h->opt.max_AL_iter; ++ou) {
+    // the handle-wide bounds, or with per-element budgets the largest (an element past its own is inert)
+    const int n_outer = outer_bound(h), n_inner = inner_bound(h);
+    for (int ou = 0; ou < n_outer; ++ou) {
         tm.cut();
-        launch_outer_begin(h->p, h->d, h->stream);
+        launch_outer_begin(h->p, h->d, budget_of(h), h->stream);
         outers++;
-        for (int in = 0; in < h->opt.max_DDP_iter; ++in) {
+        for (int in = 0; in < n_inner; ++in) {
             if (graph) {
                 // iteration `in` was launched by the step before (or here, for the first); the next
                 // one is queued before waiting for this one's count, so the GPU never waits on the
@@ -299,7 +302,7 @@ extern "C" int hsddp_solve(hsddp_handle h, hsddp_stats *stats)
                 int n = 0;
                 tm.cut();
                 if (in == 0 && (rc = graph_launch(h, trials, 0))) return rc;
-                if (in + 1 < h->opt.max_DDP_iter && (rc = graph_launch(h, trials, (in + 1) & 1))) return rc;
+                if (in + 1 < n_inner && (rc = graph_launch(h, trials, (in + 1) & 1))) return rc;
                 if ((rc = graph_wait(h, in & 1, n))) return rc;
                 iters++;
                 nbwd++;
@@ -332,7 +335,7 @@ extern "C" int hsddp_solve_begin(hsddp_handle h)
     int rc = solve_check(h);
     if (rc) return rc;
     begin_launches(h);
-    launch_outer_begin(h->p, h->d, h->stream);
+    launch_outer_begin(h->p, h->d, budget_of(h), h->stream);
     HIPCHK(hipGetLastError());
     return HSDDP_OK;
 }

@@ -10,6 +10,10 @@
 //                                     (HKDMPC.cpp:96-165, 207-298)
 //   simulate_policy(...)              the solved policy simulated from given states
 //                                     (hsddp_simulate_policy)
+//   restart(robots, windows, states)  the named robots start again as new problems in the next
+//                                     update(): HKDMPCSolver::initialize for them (HKDMPC.cpp:20-94)
+//                                     beside ::update for the rest (hsddp_restart_elements,
+//                                     hsddp_set_element_budgets; mpc_config.per_robot_windows)
 //   update_closed_loop()              update() with the plant on the device: the next initial state
 //                                     is the policy's own simulation of the steps between two updates
 //                                     (closed_loop = true makes the message handler run it)
@@ -52,6 +56,9 @@ struct MPCConfig {
     float plan_duration = 0.6f;
     int nsteps_between_mpc = 1;
     float timeStep = 0.01f;
+    // every robot with its own reference window and phase layout (desc.ref_per_element): robots can
+    // then be restarted one by one (restart()); off: the batch shares one window, as one robot's
+    bool per_robot_windows = false;
 };
 
 class HKDMPCSolver {
@@ -100,14 +107,14 @@ public:
         desc.n_phases = plan.n_phases;
         for (int i = 0; i < plan.n_phases; ++i) desc.horizons[i] = plan.horizons[i];
         desc.dt = mpc_config.timeStep;
-        desc.ref_per_element = 0;
+        desc.ref_per_element = mpc_config.per_robot_windows ? 1 : 0;
         hsddp_default_weights(&desc.weights);
         hsddp_default_constraint_params(&desc.cparams);
         chk(hsddp_create(&desc, &h));
         chk(hsddp_set_options(h, &ddp_options));
         chk(hsddp_set_reference_table(h, quad_reference.data(), (int)quad_reference.size(), dt_ref));
-        const int ws = 0;
-        chk(hsddp_build_references(h, &ws, n_win, nullptr, mpc_config.timeStep));
+        const std::vector<int> ws(mpc_config.per_robot_windows ? B : 1, 0);
+        chk(hsddp_build_references(h, ws.data(), n_win, nullptr, mpc_config.timeStep));
         P = plan.n_phases;
         std::vector<int> contacts((size_t)B * (P + 1) * 4);
         for (int b = 0; b < B; ++b)
@@ -128,6 +135,30 @@ public:
         mpc_time = 0;
         mpc_time_prev = 0;
         mpc_iter = 0;
+        mpc_time0.assign(B, 0.0);
+        restarted.assign(B, 0);
+        pending_robots.clear();
+    }
+
+    // The named robots start again in the next update(), each as a new problem at table sample
+    // window_starts[j] with the measured state states[j] (which replaces that robot's message for
+    // the tick).  The tick's order is advance -> restart -> x0 -> solve: advancing a robot that is
+    // then restarted is harmless, because the restart overwrites everything the advance touched
+    // for it.  The restarted robots solve with the options' max_AL_iter / max_DDP_iter, as
+    // initialize() does, the others with update()'s pair (quirk A17), in the same solve; a restarted
+    // robot's mpc_time starts from 0 again, as after initialize().
+    void restart(const std::vector<int> &robots, const std::vector<int> &window_starts,
+                 const std::vector<hkd_data_lcmt> &states)
+    {
+        if (robots.size() != window_starts.size() || robots.size() != states.size())
+            throw std::runtime_error("restart: one window start and one state per robot");
+        for (int b : robots)
+            if (b < 0 || b >= B) throw std::runtime_error("restart: no such robot");
+        wait();
+        std::lock_guard<std::mutex> lk(mpc_mutex);
+        pending_robots = robots;
+        pending_windows = window_starts;
+        pending_states = states;
     }
 
     // HKDMPCSolver::mpcdata_lcm_handler (HKDMPC.cpp:166-200): msgs[B]
@@ -179,6 +210,7 @@ public:
         o.max_DDP_iter = 1;
         chk(hsddp_set_options(h, &o));
         mpc_iter++;
+        for (size_t j = 0; j < pending_robots.size(); ++j) hkd_data[pending_robots[j]] = pending_states[j];
         robot_states.resize(B);
         for (int b = 0; b < B; ++b) {
             const hkd_data_lcmt &m = hkd_data[b];
@@ -198,6 +230,23 @@ public:
         // qdummy] from the robot states (HKDMPC.cpp:118-134) with the contacts the advance derived
         std::vector<int> flags(mpc_config.nsteps_between_mpc);
         chk(hsddp_advance(h, mpc_config.nsteps_between_mpc, mpc_config.plan_duration, dt_mpc, nullptr, flags.data()));
+        if (!pending_robots.empty()) {  // (after the advance: the restart overwrites what it did to these robots)
+            std::vector<int> mask(B, 0), ws(B, 0), al(B, o.max_AL_iter), ddp(B, o.max_DDP_iter);
+            for (size_t j = 0; j < pending_robots.size(); ++j) {
+                const int b = pending_robots[j];
+                mask[b] = 1;
+                ws[b] = pending_windows[j];
+                al[b] = ddp_options.max_AL_iter;   // HKDMPCSolver::initialize's budget
+                ddp[b] = ddp_options.max_DDP_iter;
+                mpc_time0[b] = mpc_time;
+                restarted[b] = 1;
+            }
+            chk(hsddp_restart_elements(h, mask.data(), ws.data(), mpc_config.plan_duration, dt_mpc, nullptr));
+            chk(hsddp_set_element_budgets(h, al.data(), ddp.data()));
+        } else {
+            chk(hsddp_set_element_budgets(h, nullptr, nullptr));
+        }
+        pending_robots.clear();
         chk(hsddp_update_problem_measured(h, nullptr, robot_states.data(), 0, nullptr, nullptr, nullptr));
         const auto t0 = std::chrono::high_resolution_clock::now();
         hsddp_stats st;
@@ -208,11 +257,25 @@ public:
         commands.resize(B);
         chk(hsddp_extract_commands_measured(h, mpc_config.nsteps_between_mpc, mpc_time, dt_mpc, nullptr, 0, solve_time,
                                             commands.data(), 0));
+        // a robot restarted at mpc_time t0 counts its own time from there (rounded twice, as the
+        // extraction rounds mpc_time + k dt_mpc)
+        for (int b = 0; b < B; ++b) {
+            if (!restarted[b]) continue;
+            const double tb = mpc_time - mpc_time0[b];
+            for (int k = 0; k < commands[b].N_mpcsteps; ++k) {
+                // the product is rounded before the sum, as the device forms it: the volatile keeps
+                // the compiler from contracting the two into one fused multiply-add
+                volatile double step = (double)k * (double)dt_mpc;
+                commands[b].mpc_times[k] = tb + step;
+            }
+        }
         if (publish) publish(commands);
         // P and the durations member, for callers that read them: host copies of what the handle
-        // holds, after the commands have left
-        int hz[HSDDP_MAX_PHASES];
-        chk(hsddp_get_layout(h, &P, hz, nullptr, nullptr));
+        // holds, after the commands have left (P: the largest robot's with per-robot layouts)
+        std::vector<int> nph(B);
+        chk(hsddp_get_element_layouts(h, nph.data(), nullptr, nullptr, nullptr));
+        P = 0;
+        for (int v : nph) P = v > P ? v : P;
         durations.assign((size_t)B * P * 4, 0.0);
         chk(hsddp_get_phase_info(h, nullptr, durations.data()));
     }
@@ -283,6 +346,8 @@ public:
     bool closed_loop = false;              // the message handler runs update_closed_loop()
     std::vector<hsddp_sim_sample> plant;   // the plant's outcome per robot in the last closed-loop update
     double mpc_time = 0, mpc_time_prev = 0;
+    std::vector<double> mpc_time0;  // per robot: the mpc_time of its last restart
+    std::vector<char> restarted;    // per robot: restarted since initialize() (mpc_time0 holds a time)
     float solve_time;
     int mpc_iter = 0, P = 0;
     hsddp_handle h = nullptr;
@@ -322,6 +387,8 @@ private:
                     for (int a = 0; a < 3; ++a) x0[(size_t)b * 24 + 12 + 3 * l + a] = pfo[((size_t)b * 4 + l) * 3 + a];
     }
 
+    std::vector<int> pending_robots, pending_windows;  // restart(): applied by the next update()
+    std::vector<hkd_data_lcmt> pending_states;
     std::mutex mpc_mutex;
     std::thread worker;
     std::exception_ptr worker_error;

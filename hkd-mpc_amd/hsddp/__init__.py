@@ -174,6 +174,22 @@ class Solver:
         self.options = options
         check(lib().hsddp_set_options(self._h, C.byref(options)))
 
+    def set_element_budgets(self, max_AL=None, max_DDP=None) -> None:
+        """Per-element loop bounds (hsddp_set_element_budgets): element b runs max_AL[b] outer
+        iterations of max_DDP[b] inner iterations each in place of the options' max_AL_iter /
+        max_DDP_iter; both None: back to the handle-wide options.  solver_info then needs
+        capacity >= 1 + max(max_AL * max_DDP)."""
+        if max_AL is None and max_DDP is None:
+            check(lib().hsddp_set_element_budgets(self._h, None, None))
+            return
+        if max_AL is None or max_DDP is None:
+            raise HSDDPError("set_element_budgets: both arrays or neither")
+        al = np.ascontiguousarray(np.asarray(max_AL, dtype=np.int32).reshape(-1))
+        dd = np.ascontiguousarray(np.asarray(max_DDP, dtype=np.int32).reshape(-1))
+        if al.shape != (self.B,) or dd.shape != (self.B,):
+            raise HSDDPError(f"max_AL / max_DDP: shapes {al.shape} / {dd.shape}, expected ({self.B},)")
+        check(lib().hsddp_set_element_budgets(self._h, ip(al), ip(dd)))
+
     def warm_start(self, Xbar=None, Ubar=None, K=None) -> None:
         keep = [np.ascontiguousarray(a, dtype=np.float64) if a is not None else None for a in (Xbar, Ubar, K)]
         check(lib().hsddp_upload_warm_start(self._h, *(None if a is None else dp(a) for a in keep)))
@@ -487,6 +503,28 @@ class Solver:
         self._follow_layout()
         check(rc)
         return [int(f) for f in flags[:n_steps]]
+
+    def restart_elements(self, mask, window_start, x0=None, plan_duration: float = 0.6, dt_mpc: float = 0.01) -> None:
+        """HKDProblem::initialization for the elements with mask[b] != 0 of the live batch
+        (hsddp_restart_elements): each starts again as a new problem at table sample window_start[b]
+        — new layout, contacts, references, Xbar = reference, Ubar = K = 0, initial constraint
+        parameters, x0[b] — while every other element keeps all it holds.  mask, window_start [B],
+        x0 [B][24]; entries outside the mask are not read.  x0 None: the inputs stay pending, call
+        update_problem(None, x0) / update_problem_measured / update_problem_simulated next."""
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.int32)
+        ws = np.ascontiguousarray(np.asarray(window_start, dtype=np.int32).reshape(-1))
+        if m.shape != (self.B,) or ws.shape != (self.B,):
+            raise HSDDPError(f"mask / window_start: shapes {m.shape} / {ws.shape}, expected ({self.B},)")
+        xs = None if x0 is None else np.ascontiguousarray(x0, dtype=np.float64)
+        if xs is not None and xs.shape != (self.B, 24):
+            raise HSDDPError(f"x0: shape {xs.shape}, expected ({self.B}, 24)")
+        rc = lib().hsddp_restart_elements(self._h, ip(m), ip(ws), float(plan_duration), float(dt_mpc),
+                                          None if xs is None else dp(xs))
+        P, S = C.c_int(), C.c_int()  # (the strides alone: no walk over the B layouts)
+        check(lib().hsddp_get_strides(self._h, C.byref(P), C.byref(S)))
+        self.P, self.S = P.value, S.value
+        self._contacts = None
+        check(rc)
 
     # -- policy simulation (hsddp_simulate_policy) ---------------------------------------------
     def simulate_policy(self, x_init=None, n_steps: int = 1, n_samples: int | None = None,

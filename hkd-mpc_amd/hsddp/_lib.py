@@ -125,6 +125,7 @@ EXPORTS = [
     "hsddp_extract_commands_async", "hsddp_commands_wait",
     "hsddp_simulate_policy", "hsddp_update_problem_simulated",
     "hsddp_hkd_state", "hsddp_update_problem_measured", "hsddp_extract_commands_measured",
+    "hsddp_restart_elements", "hsddp_set_element_budgets", "hsddp_get_strides",
 ]
 
 
@@ -212,6 +213,10 @@ def lib():
         L.hsddp_update_problem_measured.argtypes = [V, IP, V, C.c_int, DP, DP, DP]
         L.hsddp_extract_commands_measured.argtypes = [V, C.c_int, C.c_double, C.c_double, V, C.c_int, C.c_float, V,
                                                       C.c_int]
+    if hasattr(L, "hsddp_restart_elements"):  # (older A/B builds lack the restart)
+        L.hsddp_restart_elements.argtypes = [V, IP, IP, C.c_float, C.c_float, DP]
+        L.hsddp_set_element_budgets.argtypes = [V, IP, IP]
+        L.hsddp_get_strides.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     _lib = L
     return L
 

@@ -19,6 +19,7 @@
  *   hsddp_upload/download_constraint_params   PathConstraintBase / TerminalConstraintBase params (ReB, AL)
  *                                             ConstraintsBase.h:88-183, 329-405
  *   hsddp_solve                               MultiPhaseDDP::solve                  MultiPhaseDDP.cpp:232-428
+ *   hsddp_set_element_budgets                 the loop bounds max_AL_iter / max_DDP_iter per element  MultiPhaseDDP.cpp:257, 304
  *   hsddp_solve_begin/_iterate/_end           the same loop split at its inner iterations (:257-303 / :304-381 / :383-408)
  *   hsddp_download_trajectory                 Trajectory fields read by the caller  HKDMPC.cpp:243-298
  *   hsddp_download_element_info               get_actual_cost                       MultiPhaseDDP.h:416
@@ -27,6 +28,8 @@
  *   hsddp_plan_phases                         HKDProblem::initialization (segmentation) HKDProblem.cpp:15-68
  *   hsddp_set_reference_table / _build_references  HKDSinglePhaseReference::get_reference_at_t HKDReference.cpp:8-57
  *   hsddp_advance / hsddp_get_phase_info      HKDProblem::update from the reference table   HKDProblem.cpp:117-222
+ *   hsddp_restart_elements                    HKDProblem::initialization for some elements of a live batch
+ *                                             (HKDMPCSolver::initialize beside ::update)  HKDProblem.cpp:15-111; HKDMPC.cpp:20-94
  *   hsddp_shift / hsddp_update_problem        HKDProblem::update + HKDMPCSolver::update's re-solve
  *                                             setup (warm start reused)  HKDProblem.cpp:117-222; HKDMPC.cpp:96-143
  *   hsddp_set_layout                          a caller-side HKDProblem::update's layout + SinglePhase::
@@ -349,6 +352,9 @@ int hsddp_shift(hsddp_handle h, int n_steps, const int *contact_change);
 int hsddp_shift_elements(hsddp_handle h, int n_steps, const int *contact_change);
 /* every element's layout: n_phases [B], horizons, shooting states, is_phase_reach_end [B][16] (any NULL) */
 int hsddp_get_element_layouts(hsddp_handle h, int *n_phases, int *horizons, int *shooting, int *reach_end);
+/* the strides of the per-phase and per-slot arrays the downloads fill: the layout's P and S, or with
+ * per-element layouts the largest element's (either may be NULL).  No device work. */
+int hsddp_get_strides(hsddp_handle h, int *n_phases, int *state_slots);
 /* current layout: n_phases, horizons[16], shooting states[16], is_phase_reach_end[16] (any NULL);
  * HSDDP_ERR_UNSUPPORTED with per-element layouts (hsddp_get_element_layouts) */
 int hsddp_get_layout(hsddp_handle h, int *n_phases, int *horizons, int *shooting, int *reach_end);
@@ -401,6 +407,62 @@ int hsddp_update_problem(hsddp_handle h, const int *contacts, const double *x0, 
  * that change faster than the simulation step (tests/test_gpu_td_overflow.py). */
 int hsddp_advance(hsddp_handle h, int n_steps, float plan_duration, float dt_mpc, const double *x0,
                   int *contact_change);
+/* HKDProblem::initialization (HKDProblem.cpp:15-111) for the elements b with mask[b] != 0 of a live
+ * handle: what HKDMPCSolver::initialize builds for one robot (HKDMPC.cpp:20-94) while the other
+ * robots of the batch stay in their HKDMPCSolver::update (:97-166).  mask [B]; window_start [B] and
+ * x0 [B][24] are read at the masked entries only.  Per masked element, on the host: the
+ * segmentation of hsddp_plan_phases (HKDProblem.cpp:15-68) on its window of the table at
+ * window_start[b] (the window length and dt_sim of hsddp_build_references) gives its new layout
+ * (every state a shooting state, :104), contact rows (row P: the contact at plan_duration + dt_mpc),
+ * contact durations; its is_phase_reach_end flags are cleared (quirk A15), its window start is
+ * window_start[b] and its QuadReference clock restarts at 0.  The handle moves to per-element
+ * layouts as hsddp_shift_elements does, unless every element ends on one layout (every element
+ * restarted onto one, or elements of a shared-layout handle restarted onto that layout; elements of
+ * a per-element handle that come to agree stay per element until the next shift).  On the device the
+ * element becomes a new problem's, as hsddp_upload_problem + hsddp_upload_warm_start(h, NULL, NULL,
+ * NULL) leave one on a new handle: the references of the new layout (HKDReference.cpp:8-57), Xbar =
+ * X = ref_x (HKDProblem.cpp:84-90), Ubar = U = 0, K = 0, Defect = dX = dU = 0, the ReB pair of
+ * desc.cparams at every knot, one touchdown constraint per phase with the initial AL parameters
+ * (add_tconstr_one_phase, :104), stored constraint values zero, the per-element solver state and
+ * solver-info count cleared, and x0[b].  x0 NULL: the inputs are left pending as hsddp_advance with
+ * x0 = NULL leaves them (hsddp_update_problem with NULL contacts, hsddp_update_problem_measured or
+ * hsddp_update_problem_simulated next).  Every other element keeps its rows, parameters, stored
+ * values, layout, window and clock.  An MPC tick with restarts is hsddp_advance(x0 = NULL), this
+ * call, the x0 update, hsddp_solve: advancing an element that is then restarted is harmless, the
+ * restart overwrites all the advance touched of it.
+ * The work, on the host and on the device, follows the number of masked elements (an empty mask
+ * launches nothing): on a handle with per-element layouts the masked elements' layout records,
+ * sweep pairs and table rows are patched in place.  Two cases take one pass over the batch, as a
+ * shift does: the call that moves a shared-layout handle to per-element layouts, and a restart that
+ * changes the batch's largest phase count — the per-phase and per-slot buffers are strided by it, so
+ * the other elements' rows move to the new strides and every element's references are rebuilt.
+ * HSDDP_RESTART_TIMING=1 prints the device time of the call's kernels (HIP events) to stderr.
+ * A simulation held (hsddp_simulate_policy) and the measured foot placements of the tick
+ * (hsddp_update_problem_measured) are dropped.
+ * HSDDP_ERR_UNSUPPORTED: references not built from a table (hsddp_set_reference_table +
+ * hsddp_build_references); shared references (ref_per_element = 0) unless the mask selects every
+ * element with one window start.  HSDDP_ERR_ARG: NULL mask or window_start, a window start outside
+ * the table, a window whose horizons do not sum to Kc, no contacts / references of the current
+ * layout on the handle (a shift still awaiting them).  A refused call leaves the handle unchanged. */
+int hsddp_restart_elements(hsddp_handle h, const int *mask, const int *window_start, float plan_duration,
+                           float dt_mpc, const double *x0);
+
+/* MultiPhaseDDP::solve's loop bounds per element: element b runs the reference's loops with
+ * max_AL_iter[b] outer iterations (MultiPhaseDDP.cpp:257) of max_DDP_iter[b] inner iterations each
+ * (:304) in place of hsddp_options::max_AL_iter / max_DDP_iter — in one batch, the robots restarted
+ * this tick take HKDMPCSolver::initialize's budget (HKDMPC.cpp:20-94) and the others the _runtime
+ * pair of ::update (:97-166; hkd_mpc.hpp, quirk A17).  Both arrays [B]; both NULL: back to the
+ * handle-wide options.  The host loops to the largest bounds and an element past its own bound is
+ * inert, exactly as one whose early-exit test fired; with no_early_exit = 1 an element runs exactly
+ * its own max_AL_iter x max_DDP_iter inner iterations.  The AL / ReB update at the end of an
+ * element's last outer iteration happens as in a handle-wide solve with that budget, so every
+ * element ends as in a handle-wide solve with its own pair.  hsddp_stats keeps its meaning
+ * (inner_iterations / outer_iterations: the iterations the host ran, the maximum over elements
+ * with early exits); the solver-info history is sized for the largest budget.  The budgets stay in
+ * force over later solves and hsddp_set_options calls until they are changed or cleared.
+ * HSDDP_ERR_ARG: one array NULL, a negative bound, max_AL_iter[b] x max_DDP_iter[b] beyond the
+ * solver-info history (2^20 entries); the handle then keeps the budgets it had. */
+int hsddp_set_element_budgets(hsddp_handle h, const int *max_AL_iter, const int *max_DDP_iter);
 /* The handle's phase bookkeeping: contacts [B][P+1][4] (row P: the last phase's next contact) and,
  * for references built from a table, the phases' contact durations [B][P][4] (either may be NULL). */
 int hsddp_get_phase_info(hsddp_handle h, int *contacts, double *durations);

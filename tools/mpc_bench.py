@@ -19,6 +19,13 @@ route without the ingest (advance with pending inputs, phase_info's contacts, th
 primitive on 4 B replicated rows, update_problem(None, x0)); --measured is advance +
 update_problem_measured, with the commands from extract_commands_measured.  "advance" is then the
 whole of it, "state" the part after hsddp_advance.
+
+--restart-frac F restarts a seeded set of round(F B) robots (at least one when F > 0) every tick at
+the sample their windows have reached (hsddp_restart_elements between the advance with pending
+inputs and update_problem(None, x0)): the handle then has per-robot reference windows, also at
+F = 0 (an empty mask), and "restart" is the call's time per tick beside advance (which includes
+the x0 update) and solve.  "reupload_all" is the only route without the call — hsddp_upload_problem
++ hsddp_upload_warm_start of the whole batch — timed the same way after the ticks.
 """
 import argparse
 import json
@@ -59,9 +66,11 @@ def main():
                     help="x0 of every tick formed on the host from measured records (the route without the ingest)")
     ap.add_argument("--measured", action="store_true",
                     help="x0 of every tick formed on the device from the same records (update_problem_measured)")
+    ap.add_argument("--restart-frac", type=float, default=None,
+                    help="restart this fraction of the robots every tick (per-robot reference windows; 0: an empty mask)")
     args = ap.parse_args()
-    if args.host_state + args.measured + args.closed_loop > 1:
-        ap.error("--host-state, --measured and --closed-loop are separate legs")
+    if args.host_state + args.measured + args.closed_loop + (args.restart_frac is not None) > 1:
+        ap.error("--host-state, --measured, --closed-loop and --restart-frac are separate legs")
     B = args.batch
     tab, dt = hsddp.load_quad_reference(os.path.join(ROOT, "tests", "golden", "ref_trot.csv"))
     rng = np.random.default_rng(7)
@@ -69,12 +78,17 @@ def main():
     x0[:, 5] = 0.25
     x0[:, 12:] = np.tile(np.float32([.2, -.14, 0, .2, .14, 0, -.2, -.14, 0, -.2, .14, 0]), 1)
     x0[:, 6:12] += rng.uniform(-.2, .2, (B, 6))
-    p = hsddp.reference_problem(tab, dt, [0], x0)
+    restarts = args.restart_frac is not None
+    p = hsddp.reference_problem(tab, dt, [0] * B if restarts else [0], x0)
     s = hsddp.Solver(p, hsddp.load_settings())
     s.solve()
     s.set_options(hsddp.load_settings(max_AL_iter=2, max_DDP_iter=1))
     feet = np.tile(np.float32([.2, -.14, 0, .2, .14, 0, -.2, -.14, 0, -.2, .14, 0]), (B, 1))
-    t_adv, t_solve, t_cmd, t_plant, t_state = [], [], [], [], []
+    t_adv, t_solve, t_cmd, t_plant, t_state, t_restart = [], [], [], [], [], []
+    n_restart = 0
+    if restarts and args.restart_frac > 0:
+        n_restart = min(B, max(1, int(round(args.restart_frac * B))))
+    rng_r = np.random.default_rng(11)
     legs = np.tile(np.arange(4, dtype=np.int32), B)
     plant_ok = True
     flags = 0
@@ -106,6 +120,17 @@ def main():
                 xt[:, 12:][on] = fp[on]
                 s.update_problem(None, xt)
             t_state.append(time.perf_counter() - ts)
+        elif restarts:
+            xt = x0 + rng.uniform(-.01, .01, x0.shape)
+            mask = np.zeros(B, np.int32)
+            mask[rng_r.choice(B, n_restart, replace=False)] = 1
+            ws = np.full(B, it + 1, np.int32)  # the sample every robot's window has reached
+            t0 = time.perf_counter()
+            flags += sum(s.advance(None, 1))
+            tr = time.perf_counter()
+            s.restart_elements(mask, ws)
+            t_restart.append(time.perf_counter() - tr)
+            s.update_problem(None, xt)
         else:
             xt = x0 + rng.uniform(-.01, .01, x0.shape)
             t0 = time.perf_counter()
@@ -130,7 +155,9 @@ def main():
         t5 = time.perf_counter()
         cmd = s.commands_wait(ticket, copy=False)
         t_last = time.perf_counter() - t5
-    lay = s.layout()
+    lay = s.element_layouts() if restarts else s.layout()
+    if restarts:
+        lay = {"horizons": [int(v) for v in lay["horizons"][0]]}
     finite = bool(np.isfinite(s.element_info()["cost"]).all()) and bool(np.isfinite(cmd["hkd_controls"]).all())
     S, Kc = sum(n + 1 for n in lay["horizons"]), sum(lay["horizons"])
     # k_shift_gather moves every element's warm start once: Xbar [S][24], Ubar [Kc][24] and the
@@ -148,6 +175,19 @@ def main():
         out["metric"] = "closed-loop MPC tick (plant + advance + solve + extract), HKD trot reference file"
         out["ms_per_tick_median"]["plant"] = med(t_plant)
         out["plant_all_ok"] = plant_ok
+    if restarts:
+        out["metric"] = "MPC tick with restarts (advance + restart + x0 + solve + extract), HKD trot reference file"
+        out["restarted_per_tick"] = n_restart
+        out["ms_per_tick_median"]["advance"] = med(np.array(t_adv) - np.array(t_restart))
+        out["ms_per_tick_median"]["restart"] = med(t_restart)
+        t_up = []
+        for _ in range(5):  # the whole batch as a new problem: hsddp_upload_problem + hsddp_upload_warm_start
+            c = s.phase_info()["contacts"]
+            tu = time.perf_counter()
+            s.upload_problem(c, x0)
+            s.warm_start()
+            t_up.append(time.perf_counter() - tu)
+        out["ms_per_tick_median"]["reupload_all"] = med(t_up)
     if args.host_state or args.measured:
         out["metric"] = ("MPC tick from measured robot states, x0 formed on the %s, HKD trot reference file"
                          % ("device (update_problem_measured)" if args.measured else "host (foot-position primitive)"))
