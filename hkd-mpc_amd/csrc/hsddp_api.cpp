@@ -9,7 +9,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 
 #include "hsddp_handle.h"
 #include "hsddp_measure.h"
@@ -363,19 +362,7 @@ int hsddp::set_layouts(hsddp_handle h, const std::vector<Layout> &lays)
     const int B = p.B;
     int Pmax = 0, Smax = 0, tail = 0;
     for (auto &L : lays) { Pmax = std::max(Pmax, L.P); Smax = std::max(Smax, L.S); tail |= L.has_tail; }
-    std::map<std::vector<int>, std::vector<int>> groups;
-    for (int b = 0; b < B; ++b) {
-        std::vector<int> key(lays[b].N, lays[b].N + lays[b].P);
-        key.push_back(-1);
-        key.insert(key.end(), lays[b].ss, lays[b].ss + lays[b].P);
-        groups[key].push_back(b);
-    }
-    std::vector<int> pairs;
-    for (auto &g : groups)
-        for (size_t j = 0; j < g.second.size(); j += 2) {
-            pairs.push_back(g.second[j]);
-            pairs.push_back(j + 1 < g.second.size() ? g.second[j + 1] : -1);
-        }
+    std::vector<int> pairs = pair_layouts(lays);  // (patched in place by hsddp_restart_elements: patch_pairs)
     HIPCHK(hipSetDevice(h->desc.device));
     HIPCHK(hipMemcpy((void *)h->d.lay, lays.data(), B * sizeof(Layout), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy((void *)h->d.pairs, pairs.data(), pairs.size() * sizeof(int), hipMemcpyHostToDevice));

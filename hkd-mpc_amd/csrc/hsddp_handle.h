@@ -1,7 +1,8 @@
 // hsddp_handle.h — the handle behind include/hsddp.h and the host helpers its source files share
 // (private to csrc): hsddp_api.cpp (handle, layouts, transfers), hsddp_solve.cpp (the solve loop),
-// hsddp_horizon.cpp (the MPC caller's side: commands, shift, references, hsddp_advance) and
-// hsddp_settings.cpp (defaults and the INFO loaders).
+// hsddp_horizon.cpp (the MPC caller's side: commands, shift, references, hsddp_advance, restarts)
+// and hsddp_settings.cpp (defaults and the INFO loaders).  The host bookkeeping those entry points
+// plan with is hsddp_phases.cpp, which sees the handle's host fields through view_of() only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -169,6 +170,24 @@ inline const Layout &layout_of(hsddp_handle h, size_t b)
 inline const int *reach_of(hsddp_handle h, size_t b)
 {
     return h->lays.empty() ? h->reach_end.data() : &h->reach_el[b * HSDDP_MAX_PHASES];
+}
+
+// the handle's host state as the bookkeeping reads it (hsddp_phases.h): pointers into the handle's
+// own fields, good until a call changes them
+inline HorizonView view_of(hsddp_handle h)
+{
+    HorizonView v{};
+    v.B = h->p.B; v.Bref = h->Bref; v.Kc = h->p.Kc; v.P = h->p.P; v.S = h->p.S;
+    v.S_cap = h->S_cap;
+    v.shared = &h->shared;
+    v.lays = h->lays.empty() ? nullptr : h->lays.data();
+    v.reach = v.lays ? h->reach_el.data() : h->reach_end.data();
+    v.contacts = h->contacts.data(); v.durations = h->durations.data();
+    v.table = h->table_host.data(); v.ref_n = h->ref_n; v.ref_dt = h->ref_dt;
+    v.win_start = h->win_start.data(); v.win_len = h->win_len; v.dt_sim = h->dt_sim;
+    v.t_cur = h->t_cur;
+    v.t_el = h->t_el.empty() ? nullptr : h->t_el.data();
+    return v;
 }
 
 // the budgets the kernels read (null: the handle-wide options) and the host's loop bounds

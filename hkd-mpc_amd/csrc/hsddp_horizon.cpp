@@ -1,16 +1,18 @@
 // hsddp_horizon.cpp — the MPC caller's side of the C-ABI, around the solve: command extraction
 // (HKDMPCSolver::update_foot_placement + publish_mpc_cmd), the receding-horizon shift
-// (HKDProblem::update, HKDProblem.cpp:117-222; its bookkeeping is hsddp_phases.cpp), the reference
-// table and the per-slot references built from it, hsddp_advance, which steps all of them from
-// the table, and hsddp_restart_elements, which starts single elements again as new problems.
+// (HKDProblem::update, HKDProblem.cpp:117-222), the reference table and the per-slot references
+// built from it, hsddp_advance, which steps all of them from the table, and
+// hsddp_restart_elements, which starts single elements again as new problems.  What is here is the
+// device and the handle: argument and state checks, allocations, copies, launches,
+// synchronisations, buffer swaps and the handle's flags.  The bookkeeping (which phases, rows,
+// slot maps, strides, pairs and clocks follow) is planned in hsddp_phases.cpp from a read-only
+// view of the handle (view_of), so each entry point reads: check, plan, apply, commit.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <map>
 
 #include "hsddp_handle.h"
 #include "hsddp_mpc.h"
@@ -180,28 +182,6 @@ extern "C" int hsddp_commands_wait(hsddp_handle h, int ticket, const hsddp_mpc_c
 }
 
 // ---- receding-horizon shift (HKDProblem::update, HKDProblem.cpp:117-222) ----------------------
-namespace {
-// the bookkeeping's outcome: per slot map the phases after the steps (PhaseStepper) and their
-// layout, and the map of each element (elements with equal layout, reach flags and step flags
-// share one)
-struct ShiftPlan {
-    std::vector<std::vector<ShiftPhase>> phs;
-    std::vector<Layout> nl;
-    std::vector<int> map_id;  // [B]
-};
-}  // namespace
-
-// the key under which elements share a slot map: horizons, shooting states, reach flags, step flags
-static std::vector<int> shift_key(const Layout &L, const int *reach, int n_steps, const int *cc)
-{
-    std::vector<int> key(L.N, L.N + L.P);
-    key.push_back(-1);
-    key.insert(key.end(), L.ss, L.ss + L.P);
-    key.insert(key.end(), reach, reach + L.P);
-    key.insert(key.end(), cc, cc + n_steps);
-    return key;
-}
-
 // The shift on the device and in the handle.  When every element ends on one layout the handle
 // keeps (or returns to) the shared layout.  A phase that would carry more than HSDDP_MAX_TD
 // touchdown constraints keeps the first ones (the shift is otherwise complete):
@@ -214,35 +194,16 @@ static int shift_apply(hsddp_handle h, const ShiftPlan &plan, bool defer, int *o
     h->slots_fresh = false;
     Params &p = h->p;
     const size_t B = p.B;
-    const std::vector<std::vector<ShiftPhase>> &phs = plan.phs;
-    const std::vector<Layout> &nl = plan.nl;
     const std::vector<int> &map_id = plan.map_id;
-    const int nk = (int)phs.size();
-    int Snew = 0, Pnew = 0;
-    for (const Layout &L : nl) {
-        if (control_slots(L) != p.Kc || (size_t)L.S > h->S_cap)
-            return fail(HSDDP_ERR_ARG, "shifted layout exceeds the handle's capacity");
-        Snew = std::max(Snew, L.S);
-        Pnew = std::max(Pnew, L.P);
-    }
-    // slot maps [nk][Snew] (padding rows: zero) and [nk][Kc]; constraint-parameter maps: ReB source
-    // per control slot [nk][Kc], phase source and appended touchdown constraints [nk][16]
-    std::vector<int> smap((size_t)nk * Snew, -1), cmap((size_t)nk * p.Kc), rmap((size_t)nk * p.Kc);
-    std::vector<int> pmap((size_t)nk * HSDDP_MAX_PHASES, -1), nadd((size_t)nk * HSDDP_MAX_PHASES, 0);
-    for (int q = 0; q < nk; ++q) {
-        size_t s = 0, k = 0, r = 0;
-        for (size_t i = 0; i < phs[q].size(); ++i) {
-            const auto &f = phs[q][i];
-            for (int v : f.xs) smap[(size_t)q * Snew + s++] = v;
-            for (int v : f.us) cmap[(size_t)q * p.Kc + k++] = v;
-            for (int v : f.rs) rmap[(size_t)q * p.Kc + r++] = v;
-            pmap[(size_t)q * HSDDP_MAX_PHASES + i] = f.src;
-            nadd[(size_t)q * HSDDP_MAX_PHASES + i] = f.add;
-        }
-    }
+    const int nk = (int)plan.phs.size();
+    ShiftMaps m;
+    std::string why;
+    int rc;
+    if ((rc = flatten_shift(plan, p.Kc, h->S_cap, m, why))) return fail(rc, why);
+    const int Snew = m.S_new, Pnew = m.P_new;
+    std::vector<int> &smap = m.smap, &cmap = m.cmap, &rmap = m.rmap, &pmap = m.pmap, &nadd = m.nadd;
     HIPCHK(hipSetDevice(h->desc.device));
     Bufs &d = h->d;
-    int rc;
     if (!h->spare_K) {  // (the new Xbar / Ubar rows go to each element's third buffer)
         void *sk;
         if (p.fp32) { float *k32; if ((rc = dalloc(h, k32, B * p.Kc * KCW))) return rc; sk = k32; }
@@ -322,17 +283,14 @@ static int shift_apply(hsddp_handle h, const ShiftPlan &plan, bool defer, int *o
     // the new layouts
     if (nk == 1) {  // one layout for the batch: the handle's own
         int reach[HSDDP_MAX_PHASES];
-        for (int i = 0; i < nl[0].P; ++i) reach[i] = phs[0][i].reach;
-        adopt_shared_layout(h, nl[0], reach);
+        plan.reach(0, reach);
+        adopt_shared_layout(h, plan.nl[0], reach);
     } else {
-        std::vector<Layout> lays(B);
-        std::vector<int> reach(B * HSDDP_MAX_PHASES, 0);
-        for (size_t b = 0; b < B; ++b) {
-            lays[b] = nl[map_id[b]];
-            for (int i = 0; i < lays[b].P; ++i) reach[b * HSDDP_MAX_PHASES + i] = phs[map_id[b]][i].reach;
-        }
+        std::vector<Layout> lays;
+        std::vector<int> reach;
+        shifted_layouts(plan, lays, reach);
         if ((rc = set_layouts(h, lays))) return rc;
-        h->reach_el = reach;
+        h->reach_el.swap(reach);
     }
     h->need_inputs = true;
     h->refs_on_device = false;  // built for the old layout
@@ -357,35 +315,10 @@ static int shift_by_flags(hsddp_handle h, int n_steps, const int *cc, size_t bst
     if (!h->have_problem) return fail(HSDDP_ERR_ARG, "upload the problem first");
     if (n_steps < 0) return fail(HSDDP_ERR_ARG, "n_steps must be >= 0");
     h->slots_fresh = false;
-    const size_t B = h->p.B;
-    std::map<std::vector<int>, int> keys;
     ShiftPlan plan;
-    plan.map_id.assign(B, 0);
-    // the handle's shared layout shifted by one set of flags (hsddp_shift): one key for the batch
-    // (a per-element key and map lookup cost ≈ 1 µs an element: 4 ms of host time at B = 4096)
-    const size_t nkey = (h->lays.empty() && bstride == 0) ? std::min<size_t>(B, 1) : B;
-    for (size_t b = 0; b < nkey; ++b) {
-        const Layout L = layout_of(h, b);
-        const int *flags = cc + b * bstride;
-        std::vector<int> key = shift_key(L, reach_of(h, b), n_steps, flags);
-        auto it = keys.find(key);
-        if (it == keys.end()) {
-            PhaseStepper st(L, reach_of(h, b));
-            Layout Ln;
-            std::string why;
-            int rc = 0;
-            for (int j = 0; j < n_steps && !rc; ++j)
-                if (!(rc = st.drop_front("shift", why))) rc = st.extend_back(flags[j], "shift", why);
-            if (rc || (rc = st.finish(Ln, why))) return fail(rc, why);
-            it = keys.emplace(std::move(key), (int)plan.phs.size()).first;
-            plan.phs.push_back(std::move(st.ph));
-            plan.nl.push_back(Ln);
-        }
-        plan.map_id[b] = it->second;
-    }
-    if (plan.phs.size() > 1 && h->Bref == 1 && B > 1)  // checked before any device work: the handle stays usable
-        return fail(HSDDP_ERR_ARG, "the elements' shifts diverge into per-element layouts, which need per-element "
-                                   "references (ref_per_element = 1)");
+    std::string why;
+    // (every refusal comes before any device work: the handle stays usable)
+    if (int rc = plan_shift(view_of(h), n_steps, cc, bstride, plan, why)) return fail(rc, why);
     h->sim_shifted += n_steps;  // (hsddp_update_problem_simulated compares it with the simulation's steps)
     return shift_apply(h, plan, false, nullptr);
 }
@@ -426,35 +359,6 @@ extern "C" int hsddp_set_reference_table(hsddp_handle h, const hsddp_quad_state 
     return HSDDP_OK;
 }
 
-// the phases' start times on the float clock of HKDProblem::initialization (t += dt_sim per knot)
-static std::vector<float> clock_starts(const Layout &L, float dt_sim)
-{
-    std::vector<float> start(L.P);
-    float t = 0.0f;
-    for (int i = 0; i < L.P; ++i) {
-        start[i] = t;
-        for (int k = 0; k < L.N[i]; ++k) t += dt_sim;
-    }
-    return start;
-}
-
-// the window sample of every state slot of layout L, S entries (padding slots repeat the last
-// sample): slot times as the reference forms them, t_offset (float, phase start relative to the
-// first phase) + k dt (double), passed on as float (SinglePhase.cpp:243-287; set_time_offset,
-// HKDProblem.cpp:103,208), snapped to a sample (QuadReference.cpp:60-76)
-static std::vector<int> slot_samples(const Layout &L, const std::vector<float> &start, float dt_sim, float dt_ref,
-                                     int sz, int S)
-{
-    std::vector<int> row(S, 0);
-    for (int i = 0; i < L.P; ++i)
-        for (int k = 0; k <= L.N[i]; ++k) {
-            const float t = (float)((double)start[i] + k * (double)dt_sim);
-            row[L.s0[i] + k] = sample_at(t, dt_ref, sz);
-        }
-    for (int sl = L.S; sl < S; ++sl) row[sl] = row[L.S - 1];
-    return row;
-}
-
 // initial: a new problem (not an hsddp_advance step): QuadReference's clock restarts and every
 // phase's contact duration is read at its start time, as HKDProblem::initialization does
 // (get_contact_duration_at_t at t = 0 and at each phase end, HKDProblem.cpp:38,63)
@@ -471,31 +375,11 @@ static int build_refs(hsddp_handle h, const int *window_start, int window_len, c
         if (window_start[b] < 0 || window_start[b] >= h->ref_n) return fail(HSDDP_ERR_ARG, "window start outside the table");
     if (elem && phase_start_times)
         return fail(HSDDP_ERR_ARG, "per-element layouts: the phase start times follow each element's own float clock (NULL)");
-    // the phases' start times, per layout: the caller's, or the float clock's
-    auto starts_of = [&](const Layout &L) {
-        if (!phase_start_times) return clock_starts(L, dt_sim);
-        std::vector<float> start(L.P);
-        for (int i = 0; i < L.P; ++i) start[i] = phase_start_times[i] - phase_start_times[0];
-        return start;
-    };
-    const int sz = window_len - 1;
-    // one slot map per distinct layout ([n_maps][S], padding slots repeat the last sample)
-    std::map<std::vector<int>, int> keys;
-    std::vector<int> idx, map_id(elem ? p.B : 0);
-    std::vector<std::vector<float>> map_starts;
-    for (int b = 0; b < (elem ? p.B : 1); ++b) {
-        const Layout L = layout_of(h, b);
-        std::vector<int> key(L.N, L.N + L.P);
-        auto it = keys.find(key);
-        if (it == keys.end()) {
-            const std::vector<float> start = starts_of(L);
-            const std::vector<int> row = slot_samples(L, start, dt_sim, h->ref_dt, sz, p.S);
-            it = keys.emplace(key, (int)map_starts.size()).first;
-            idx.insert(idx.end(), row.begin(), row.end());
-            map_starts.push_back(start);
-        }
-        if (elem) map_id[b] = it->second;
-    }
+    // one slot map per distinct layout ([n_maps][S], padding slots repeat the last sample), the phases
+    // starting at the caller's times or on the float clock
+    RefPlan rp;
+    plan_refs(view_of(h), window_start, window_len, phase_start_times, dt_sim, initial, rp);
+    const std::vector<int> &idx = rp.idx, &map_id = rp.map_id;
     HIPCHK(hipSetDevice(h->desc.device));
     char *buf;
     int rc;
@@ -518,14 +402,7 @@ static int build_refs(hsddp_handle h, const int *window_start, int window_len, c
     if (initial) {
         h->t_cur = 0;
         h->t_el.clear();
-        h->durations.assign((size_t)p.B * p.P * 4, 0.0);
-        for (int b = 0; b < p.B; ++b) {
-            const std::vector<float> &start = map_starts[elem ? map_id[b] : 0];
-            for (int i = 0; i < (int)start.size(); ++i) {
-                const int k = std::min(window_start[Br == 1 ? 0 : b] + sample_at(start[i], h->ref_dt, sz), h->ref_n - 1);
-                for (int l = 0; l < 4; ++l) h->durations[((size_t)b * p.P + i) * 4 + l] = h->table_host[k].status_dur[l];
-            }
-        }
+        h->durations.swap(rp.durations);
     }
     return HSDDP_OK;
 }
@@ -553,10 +430,6 @@ static int advance_impl(hsddp_handle h, int n_steps, float plan_duration, float 
     if (h->win_start.empty() || h->table_host.empty())
         return fail(HSDDP_ERR_ARG, "references not built from a table (hsddp_build_references)");
     if (n_steps < 0) return fail(HSDDP_ERR_ARG, "n_steps must be >= 0");
-    const Params &p = h->p;
-    const int B = p.B, Br = h->Bref, sz = h->win_len - 1;
-    const bool elem = !h->lays.empty();
-    const float dt = h->ref_dt, dts = h->dt_sim;
     // HSDDP_ADVANCE_TIMING=1: wall time of the advance's stages to stderr (a diagnostic)
     static const bool timing = std::getenv("HSDDP_ADVANCE_TIMING") != nullptr;
     using clk = std::chrono::steady_clock;
@@ -568,130 +441,26 @@ static int advance_impl(hsddp_handle h, int n_steps, float plan_duration, float 
         tstage[q] = std::chrono::duration<double, std::micro>(t - tmark).count();
         tmark = t;
     };
-    auto leq = [](float a, float b) { return a < b || std::abs(a - b) <= 1e-6f; };
-    int adv = 0;  // samples per simulation step
-    for (int i = 1; leq(i * dt, dts); ++i) adv++;
-    // QuadReference::step for every step: the window starts and the clock (shared by the batch, or
-    // each element's own once hsddp_restart_elements has set some element's back to 0)
-    const int P0 = p.P;  // stride of the current contact rows [B][P0 + 1][4] and durations [B][P0][4]
-    std::vector<std::vector<int>> wsj(n_steps);  // window starts at each step
-    std::vector<std::vector<float>> relj(n_steps);  // new_end - new_start at each step, per clock
-    std::vector<int> ws(h->win_start);
-    std::vector<float> t_cur(h->t_el.empty() ? std::vector<float>(1, h->t_cur) : h->t_el);
-    for (int j = 0; j < n_steps; ++j) {
-        for (int a = 0; a < adv; ++a) {
-            for (float &t : t_cur) t += dt;
-            for (int &w : ws) w++;
-        }
-        for (int &w : ws)
-            if (w >= h->ref_n) return fail(HSDDP_ERR_ARG, "the reference window ran past the table");
-        wsj[j] = ws;
-        for (float t : t_cur) relj[j].push_back((t + plan_duration) - t);  // new_end_time - new_start_time
-    }
-    auto rel_at = [&](int b, int j) { return relj[j][relj[j].size() == 1 ? 0 : b]; };
-    auto sample_w = [&](const std::vector<int> &w, int b, float t) -> const hsddp_quad_state & {
-        const int k = w[Br == 1 ? 0 : b] + sample_at(t, dt, sz);
-        return h->table_host[std::min(k, h->ref_n - 1)];
-    };
-    // a phase's sample: of an old phase its row of the handle's contacts / durations, of one these
-    // steps start the table's at the horizon end of its first step
-    auto phase_contact = [&](int b, const ShiftPhase &f) -> const int * {
-        return f.src >= 0 ? &h->contacts[((size_t)b * (P0 + 1) + f.src) * 4] : sample_w(wsj[f.born], b, rel_at(b, f.born)).contact;
-    };
-    auto phase_duration = [&](int b, const ShiftPhase &f) -> const double * {
-        return f.src >= 0 ? &h->durations[((size_t)b * P0 + f.src) * 4] : sample_w(wsj[f.born], b, rel_at(b, f.born)).status_dur;
-    };
-    // with the handle's shared layout and window, an element whose contact rows equal element 0's
-    // steps exactly as element 0 does (the MPC batch of one gait): its bookkeeping is element 0's
-    std::vector<int> rep(B);
-    for (int b = 0; b < B; ++b) {
-        const size_t n = (size_t)(P0 + 1) * 4;
-        rep[b] = (b > 0 && !elem && Br == 1 &&
-                  std::equal(h->contacts.begin() + (size_t)b * n, h->contacts.begin() + (size_t)(b + 1) * n, h->contacts.begin()))
-                     ? 0 : b;
-    }
-    // HKDProblem::update's bookkeeping (HKDProblem.cpp:126-202) of every element over the steps
-    // (PhaseStepper), the flag of each step read off the table: the contact at the new horizon end
-    // against the last phase's.  Beside the phases: the step flags, where the next-contact row
-    // comes from and the slot map (elements with equal layout, reach flags and step flags share one)
-    struct Walk {
-        std::vector<int> flags;
-        int P_old = 0;                       // the element's phases before the steps
-        int next_kind = 0, next_step = -1;  // row P: 0 old row, 1 contact at relj, 2 at plan + dt_mpc
-        int map = 0;
-    };
-    std::vector<Walk> wk(B);
-    ShiftPlan plan;
-    std::map<std::vector<int>, int> keys;
+    // plan: the walk over the table (every refusal of the step comes here, before the handle changes)
+    const HorizonView v = view_of(h);
+    AdvanceWalk w;
     std::string why;
     int rc;
-    for (int b = 0; b < B; ++b) {
-        if (rep[b] != b) continue;
-        Walk &W = wk[b];
-        const Layout L = layout_of(h, b);
-        PhaseStepper st(L, reach_of(h, b));
-        W.P_old = L.P;
-        W.flags.assign(n_steps, 0);
-        for (int j = 0; j < n_steps; ++j) {
-            if ((rc = st.drop_front("advance", why))) return fail(rc, why);
-            const int *nc = sample_w(wsj[j], b, rel_at(b, j)).contact, *lc = phase_contact(b, st.ph.back());
-            int cc = 0;
-            for (int l = 0; l < 4; ++l) cc |= nc[l] != lc[l];
-            if ((rc = st.extend_back(cc, "advance", why))) return fail(rc, why);
-            // a new phase carries no terminal constraint (identity reset)
-            if (st.ph.back().born == j) { W.next_kind = 1; W.next_step = j; }
-            if (st.ph.back().reach) { W.next_kind = 2; W.next_step = j; }
-            W.flags[j] = cc;
-        }
-        if (b > 0 && !elem && W.flags == wk[0].flags) continue;  // element 0's layout, reach flags and step flags: map 0
-        std::vector<int> key = shift_key(L, reach_of(h, b), n_steps, W.flags.data());
-        auto it = keys.find(key);
-        if (it == keys.end()) {
-            Layout Ln;
-            if ((rc = st.finish(Ln, why))) return fail(rc, why);
-            it = keys.emplace(std::move(key), (int)plan.phs.size()).first;
-            plan.phs.push_back(std::move(st.ph));
-            plan.nl.push_back(Ln);
-        }
-        W.map = it->second;
-    }
-    plan.map_id.resize(B);
-    for (int b = 0; b < B; ++b) plan.map_id[b] = wk[rep[b]].map;
+    if ((rc = walk_advance(v, n_steps, plan_duration, w, why))) return fail(rc, why);
     stage(0);
-    // the shift: one slot map for the batch when it agrees (the shared layout stays shared; deferred),
-    // else the elements' own (per-element layouts, which need per-element references; a touchdown
-    // overflow is reported after the rest of the step either way)
-    const bool agree = !elem && plan.phs.size() == 1;
-    if (!agree && B > 1 && Br == 1)
-        return fail(HSDDP_ERR_UNSUPPORTED, "elements disagree on a contact change, which takes per-element layouts "
-                                           "and per-element references (ref_per_element = 1)");
+    // apply: the shift, deferred when the batch agrees on one slot map (a touchdown overflow is
+    // reported after the rest of the step either way); the new rows are formed under its gather, at
+    // the new stride (v still points at the old rows, which the shift leaves alone)
     h->sim_shifted += n_steps;  // (hsddp_update_problem_simulated compares it with the simulation's steps)
-    if ((rc = shift_apply(h, plan, agree, &overflow))) return rc;
+    if ((rc = shift_apply(h, w.plan, w.agree, &overflow))) return rc;
     stage(1);
-    const int P = p.P;  // the new stride (the largest layout's with per-element layouts)
-    std::vector<int> contacts((size_t)B * (P + 1) * 4, 0);
-    std::vector<double> dur((size_t)B * P * 4, 0.0);
-    for (int b = 0; b < B; ++b) {
-        const Walk &W = wk[rep[b]];
-        const std::vector<ShiftPhase> &ph = plan.phs[W.map];
-        const int Pb = (int)ph.size();
-        for (int i = 0; i < Pb; ++i) {
-            const int *cv = phase_contact(b, ph[i]);
-            const double *dv = phase_duration(b, ph[i]);
-            for (int l = 0; l < 4; ++l) {
-                contacts[((size_t)b * (P + 1) + i) * 4 + l] = cv[l];
-                dur[((size_t)b * P + i) * 4 + l] = dv[l];
-            }
-        }
-        for (int l = 0; l < 4; ++l)
-            contacts[((size_t)b * (P + 1) + Pb) * 4 + l] =
-                W.next_kind == 0 ? h->contacts[((size_t)b * (P0 + 1) + W.P_old) * 4 + l]
-                : W.next_kind == 1 ? sample_w(wsj[W.next_step], b, rel_at(b, W.next_step)).contact[l]
-                                   : sample_w(wsj[W.next_step], b, plan_duration + dt_mpc).contact[l];
-    }
+    std::vector<int> contacts;
+    std::vector<double> dur;
+    advance_rows(v, w, h->p.P, plan_duration, dt_mpc, contacts, dur);
     stage(2);
-    if ((rc = build_refs(h, ws.data(), h->win_len, nullptr, dts, false))) return rc;
+    if ((rc = build_refs(h, w.ws.data(), h->win_len, nullptr, h->dt_sim, false))) return rc;
     stage(3);
+    // commit: contacts (with x0, or held for the update that brings it), durations, clocks
     if (x0) {
         if ((rc = hsddp_update_problem(h, contacts.data(), x0, nullptr, nullptr, nullptr))) return rc;
     } else {  // x0 follows from the new first phase's contact: hsddp_update_problem(h, NULL, x0, NULL...)
@@ -699,18 +468,14 @@ static int advance_impl(hsddp_handle h, int n_steps, float plan_duration, float 
         h->contacts_current = true;
     }
     h->durations.swap(dur);
-    if (h->t_el.empty()) h->t_cur = t_cur[0];
-    else h->t_el = t_cur;
+    if (h->t_el.empty()) h->t_cur = w.t_cur[0];
+    else h->t_el = w.t_cur;
     stage(4);
     if (timing)
         std::fprintf(stderr, "hsddp_advance us: bookkeeping %.1f shift %.1f contacts %.1f refs %.1f update %.1f\n",
                      tstage[0], tstage[1], tstage[2], tstage[3], tstage[4]);
     if (contact_change)  // per step: some element saw a contact change (the batch's flag when it agrees)
-        for (int j = 0; j < n_steps; ++j) {
-            int f = 0;
-            for (int b = 0; b < B; ++b) f |= wk[rep[b]].flags[j];
-            contact_change[j] = f;
-        }
+        std::copy(w.flags.begin(), w.flags.end(), contact_change);
     return HSDDP_OK;
 }
 
@@ -748,53 +513,11 @@ extern "C" int hsddp_advance(hsddp_handle h, int n_steps, float plan_duration, f
 // (The next set_layouts — every shift of a per-element handle — pairs the whole batch afresh.)
 static int repair_pairs(hsddp_handle h, const std::vector<int> &list)
 {
-    std::vector<int> &pr = h->pairs_host, &of = h->pair_of;
-    int np = h->p.n_pairs;
-    std::vector<int> freed, touched;
-    for (int b : list) {
-        const int q = of[b], partner = pr[2 * q] == b ? pr[2 * q + 1] : pr[2 * q];
-        pr[2 * q] = partner;
-        pr[2 * q + 1] = -1;
-        if (partner < 0) freed.push_back(q);
-        else touched.push_back(q);
-        of[b] = -1;
-    }
-    std::map<std::vector<int>, std::vector<int>> groups;
-    for (int b : list) {
-        const Layout &L = h->lays[b];
-        std::vector<int> key(L.N, L.N + L.P);
-        key.push_back(-1);
-        key.insert(key.end(), L.ss, L.ss + L.P);
-        groups[key].push_back(b);
-    }
-    for (auto &g : groups)
-        for (size_t j = 0; j < g.second.size(); j += 2) {
-            int q;
-            if (!freed.empty()) { q = freed.back(); freed.pop_back(); }
-            else q = np++;
-            if ((size_t)2 * q + 1 >= pr.size()) pr.resize((size_t)2 * q + 2, -1);
-            pr[2 * q] = g.second[j];
-            pr[2 * q + 1] = j + 1 < g.second.size() ? g.second[j + 1] : -1;
-            of[pr[2 * q]] = q;
-            if (pr[2 * q + 1] >= 0) of[pr[2 * q + 1]] = q;
-            touched.push_back(q);
-        }
-    std::sort(freed.begin(), freed.end(), std::greater<int>());
-    for (int q : freed) {  // emptied entries: the last pair moves in
-        const int last = np - 1;
-        if (q != last) {
-            pr[2 * q] = pr[2 * last];
-            pr[2 * q + 1] = pr[2 * last + 1];
-            of[pr[2 * q]] = q;
-            if (pr[2 * q + 1] >= 0) of[pr[2 * q + 1]] = q;
-            touched.push_back(q);
-        }
-        --np;
-    }
+    int np = h->p.n_pairs, rc;
+    const std::vector<int> touched = patch_pairs(h->pairs_host, h->pair_of, np, h->lays.data(), list);
     if ((size_t)np > (size_t)h->p.B) return fail(HSDDP_ERR_ARG, "sweep pairs exceed the batch");
-    int rc;
     for (int q : touched)
-        if (q < np && (rc = h2d((int *)h->d.pairs + 2 * q, &pr[2 * q], 2 * sizeof(int), h->stream))) return rc;
+        if (q < np && (rc = h2d((int *)h->d.pairs + 2 * q, &h->pairs_host[2 * q], 2 * sizeof(int), h->stream))) return rc;
     h->p.n_pairs = np;
     return HSDDP_OK;
 }
@@ -817,194 +540,71 @@ extern "C" int hsddp_restart_elements(hsddp_handle h, const int *mask, const int
                                            "hsddp_build_references)");
     Params &p = h->p;
     const int B = p.B, Br = h->Bref;
-    std::vector<int> list;
-    for (int b = 0; b < B; ++b)
-        if (mask[b]) list.push_back(b);
+    const std::vector<int> list = listed_elements(mask, B);
     const int n = (int)list.size();
     if (n == 0) return HSDDP_OK;  // nothing restarts: nothing is launched, nothing changes
-    const bool all = n == B;
-    if (!all && Br == 1)
+    if (n != B && Br == 1)
         return fail(HSDDP_ERR_UNSUPPORTED, "shared references: a restart of some elements needs per-element references "
                                            "(ref_per_element = 1)");
     if (!h->refs_on_device || !h->contacts_current || h->contacts.size() != (size_t)B * (p.P + 1) * 4 ||
         h->durations.size() != (size_t)B * p.P * 4)
         return fail(HSDDP_ERR_ARG, "no references and contacts of the current layout on the handle (after hsddp_shift: "
                                    "hsddp_build_references and hsddp_update_problem first)");
-    std::vector<RestartPlan> plans(n);
+    // plan: the listed elements' new problems and what they mean for the batch (strides, layouts,
+    // rows, slot maps, clocks); every refusal comes here
+    RestartBatch r;
     std::string why;
-    for (int m = 0; m < n; ++m) {
-        if (Br == 1 && window_start[list[m]] != window_start[0])
-            return fail(HSDDP_ERR_UNSUPPORTED, "shared references hold one window: every window start must be the same");
-        if (int rc = plan_restart(h->table_host.data(), h->ref_n, window_start[list[m]], h->win_len, h->ref_dt,
-                                  plan_duration, h->dt_sim, dt_mpc, p.Kc, plans[m], why))
-            return fail(rc, why);
-    }
-    // The batch's largest P and S after the restart (the strides of the per-phase and per-slot
-    // buffers).  Unlisted elements keep theirs, so the old strides stand unless a new layout exceeds
-    // them or a listed element alone held them; only then is every element looked at.
-    const bool elem = !h->lays.empty();
-    int Pn = 0, Sn = 0;
-    bool held = false;  // a listed element's old layout has the batch's largest P or S
-    for (int m = 0; m < n; ++m) {
-        Pn = std::max(Pn, plans[m].L.P);
-        Sn = std::max(Sn, plans[m].L.S);
-        const Layout &Lo = layout_of(h, list[m]);
-        held = held || Lo.P == p.P || Lo.S == p.S;
-    }
-    if (!all) {
-        if (!elem || !held || (Pn >= p.P && Sn >= p.S)) {
-            Pn = std::max(Pn, p.P);
-            Sn = std::max(Sn, p.S);
-        } else {
-            std::vector<char> listed(B, 0);
-            for (int b : list) listed[b] = 1;
-            for (int b = 0; b < B; ++b)
-                if (!listed[b]) {
-                    Pn = std::max(Pn, h->lays[b].P);
-                    Sn = std::max(Sn, h->lays[b].S);
-                }
-        }
-    }
-    if ((size_t)Sn > h->S_cap) return fail(HSDDP_ERR_ARG, "restarted layout exceeds the handle's capacity");
-    // one layout for the batch stays (or becomes) the handle's shared one: every element restarted
-    // onto one layout, or some elements of a shared-layout handle restarted onto that layout with no
-    // phase of it at its end.  (Elements of a per-element handle that come to agree stay per element.)
-    bool one = true;
-    for (int m = 1; m < n && one; ++m) one = !std::memcmp(&plans[m].L, &plans[0].L, sizeof(Layout));
-    if (!all)
-        one = one && !elem && !std::memcmp(&plans[0].L, &h->shared, sizeof(Layout)) &&
-              std::all_of(h->reach_end.begin(), h->reach_end.end(), [](int r) { return r == 0; });
+    int rc;
+    if ((rc = plan_restart_batch(view_of(h), list, window_start, plan_duration, dt_mpc, r, why))) return fail(rc, why);
+    const bool restride = r.restride, in_place = r.in_place;
+    // apply
     HIPCHK(hipSetDevice(h->desc.device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const bool restride = Pn != p.P || Sn != p.S;
-    // in place: the strides stand and the handle has per-element layouts already, so the listed
-    // elements' layout records, sweep pairs and table rows are patched and nothing of size B is built
-    const bool in_place = elem && !restride && !all;
-    const int P0 = p.P;
-    int rc;
-    std::vector<Layout> lays;
-    std::vector<int> reach;
-    if (!in_place && !one) {  // every element's layout and reach flags after the restart
-        lays.resize(B);
-        reach.assign((size_t)B * HSDDP_MAX_PHASES, 0);
-        for (int b = 0; b < B; ++b) {
-            lays[b] = layout_of(h, b);
-            std::copy(reach_of(h, b), reach_of(h, b) + lays[b].P, &reach[(size_t)b * HSDDP_MAX_PHASES]);
-        }
-        for (int m = 0; m < n; ++m) {
-            lays[list[m]] = plans[m].L;
-            std::fill_n(&reach[(size_t)list[m] * HSDDP_MAX_PHASES], HSDDP_MAX_PHASES, 0);
-        }
-    }
-    if (restride) {
-        // the other elements' rows to the new strides: a shift of no steps (identity maps; the listed
-        // elements' rows come out zero and are written below)
-        ShiftPlan plan;
-        plan.map_id.assign(B, 0);
-        std::map<std::vector<int>, int> keys;
-        std::vector<int> listed(B, -1);
-        for (int m = 0; m < n; ++m) listed[list[m]] = m;
-        for (int b = 0; b < B; ++b) {
-            const Layout L = listed[b] >= 0 ? plans[listed[b]].L : layout_of(h, b);
-            std::vector<int> key = listed[b] >= 0 ? std::vector<int>(L.N, L.N + L.P) : shift_key(L, reach_of(h, b), 0, nullptr);
-            key.push_back(listed[b] >= 0 ? -2 : -3);
-            auto it = keys.find(key);
-            if (it == keys.end()) {
-                std::vector<ShiftPhase> ph;
-                if (listed[b] >= 0) {
-                    for (int i = 0; i < L.P; ++i) {
-                        ShiftPhase f;
-                        f.N = L.N[i]; f.ss = L.ss[i]; f.reach = 0;
-                        f.xs.assign(f.N + 1, -1); f.us.assign(f.N, -1); f.rs.assign(f.N, -1);
-                        ph.push_back(f);
-                    }
-                } else {
-                    ph = PhaseStepper(L, reach_of(h, b)).ph;
-                }
-                it = keys.emplace(std::move(key), (int)plan.phs.size()).first;
-                plan.phs.push_back(std::move(ph));
-                plan.nl.push_back(L);
-            }
-            plan.map_id[b] = it->second;
-        }
+    if (restride) {  // the other elements' rows to the new strides (installs per-element layouts)
         const bool pending = h->need_inputs;
-        if ((rc = shift_apply(h, plan, false, nullptr, false))) return rc;
+        if ((rc = shift_apply(h, r.stride_plan, false, nullptr, false))) return rc;
         h->need_inputs = pending;
     }
-    // the layouts (a restriding shift_apply has installed the per-element ones)
-    if (one) {
+    if (r.one) {
         const int none[HSDDP_MAX_PHASES] = {0};
-        adopt_shared_layout(h, plans[0].L, none);
+        adopt_shared_layout(h, r.plans[0].L, none);
     } else if (in_place) {
         for (int m = 0; m < n; ++m) {  // (the device records go with the restart's kernel)
-            h->lays[list[m]] = plans[m].L;
+            h->lays[list[m]] = r.plans[m].L;
             std::fill_n(&h->reach_el[(size_t)list[m] * HSDDP_MAX_PHASES], HSDDP_MAX_PHASES, 0);
         }
         if ((rc = repair_pairs(h, list))) return rc;
     } else if (!restride) {
-        if ((rc = set_layouts(h, lays))) return rc;
-        h->reach_el = reach;
+        if ((rc = set_layouts(h, r.lays))) return rc;
+        h->reach_el.swap(r.reach);
     }
     // contact rows [B][P + 1][4] and durations [B][P][4]: the listed elements' new; at a new stride
-    // the others' rows move
-    const int P = p.P;
+    // the others' rows have moved
     if (restride) {
-        std::vector<int> contacts((size_t)B * (P + 1) * 4, 0);
-        std::vector<double> dur((size_t)B * P * 4, 0.0);
-        for (int b = 0; b < B; ++b) {
-            const int Pb = std::min(layout_of(h, b).P, P0);
-            std::copy_n(&h->contacts[(size_t)b * (P0 + 1) * 4], (Pb + 1) * 4, &contacts[(size_t)b * (P + 1) * 4]);
-            std::copy_n(&h->durations[(size_t)b * P0 * 4], Pb * 4, &dur[(size_t)b * P * 4]);
-        }
-        h->contacts.swap(contacts);
-        h->durations.swap(dur);
-    }
-    std::vector<int> rows((size_t)n * (P + 1) * 4, 0);  // the listed elements' rows, compacted
-    for (int m = 0; m < n; ++m) {
-        const int b = list[m], Pb = plans[m].L.P;
-        std::fill_n(&h->contacts[(size_t)b * (P + 1) * 4], (P + 1) * 4, 0);
-        std::fill_n(&h->durations[(size_t)b * P * 4], P * 4, 0.0);
-        std::copy_n(plans[m].contacts, (Pb + 1) * 4, &h->contacts[(size_t)b * (P + 1) * 4]);
-        std::copy_n(plans[m].durations, Pb * 4, &h->durations[(size_t)b * P * 4]);
-        std::copy_n(plans[m].contacts, (Pb + 1) * 4, &rows[(size_t)m * (P + 1) * 4]);
+        h->contacts.swap(r.contacts);
+        h->durations.swap(r.durations);
+    } else {
+        for (int m = 0; m < n; ++m)
+            put_restart_rows(r.plans[m], p.P, &h->contacts[(size_t)list[m] * (p.P + 1) * 4],
+                             &h->durations[(size_t)list[m] * p.P * 4]);
     }
     h->contacts_current = true;
     if (restride && (rc = h2d((void *)h->d.contacts, h->contacts.data(), h->contacts.size() * sizeof(int), h->stream)))
         return rc;
     // the window starts; references: at a new stride every element's are rebuilt; shared ones (every
     // element restarts) are built as a whole; else the kernel forms the listed elements' own
-    for (int m = 0; m < n; ++m) h->win_start[Br == 1 ? 0 : list[m]] = window_start[list[m]];
+    h->win_start = r.win_start;
     if (restride || Br == 1) {
-        const std::vector<int> ws(h->win_start);
-        if ((rc = build_refs(h, ws.data(), h->win_len, nullptr, h->dt_sim, false))) return rc;
+        if ((rc = build_refs(h, r.win_start.data(), h->win_len, nullptr, h->dt_sim, false))) return rc;
     }
     // the clocks: QuadReference's t_cur restarts for the listed elements
-    if (all) {
-        h->t_cur = 0;
-        h->t_el.clear();
-    } else {
-        if (h->t_el.empty()) h->t_el.assign(B, h->t_cur);
-        for (int b : list) h->t_el[b] = 0;
-    }
+    if (r.all) h->t_cur = 0;
+    h->t_el.swap(r.t_el);
     // the device rows: list, window starts, slot maps (one per distinct new layout), contact rows, x0
-    const int sz = h->win_len - 1;
-    std::map<std::vector<int>, int> maps;
-    std::vector<int> idx, map_id(n), start(n);
-    for (int m = 0; m < n; ++m) {
-        const Layout &L = plans[m].L;
-        std::vector<int> key(L.N, L.N + L.P);
-        auto it = maps.find(key);
-        if (it == maps.end()) {
-            const std::vector<int> row = slot_samples(L, clock_starts(L, h->dt_sim), h->dt_sim, h->ref_dt, sz, p.S);
-            it = maps.emplace(std::move(key), (int)maps.size()).first;
-            idx.insert(idx.end(), row.begin(), row.end());
-        }
-        map_id[m] = it->second;
-        start[m] = window_start[list[m]];
-    }
+    const std::vector<int> &idx = r.slots.idx, &map_id = r.map_id, &start = r.start, &rows = r.rows;
     std::vector<Layout> recs;  // the listed elements' layout records (in place: written by the kernel)
     if (in_place)
-        for (int m = 0; m < n; ++m) recs.push_back(plans[m].L);
+        for (int m = 0; m < n; ++m) recs.push_back(r.plans[m].L);
     const size_t nl = recs.size() * (sizeof(Layout) / sizeof(int));
     const size_t ni = (size_t)3 * n + idx.size() + rows.size() + nl, ib = (ni * sizeof(int) + 255) & ~(size_t)255;
     char *buf;
