@@ -86,6 +86,7 @@ struct hsddp_handle_t {
     double *ref_table = nullptr;  // reference samples [n][RT_W] (hsddp_set_reference_table)
     int ref_n = 0;
     float ref_dt = 0;
+    unsigned long long table_key = 0;  // hash of the table's samples (the element records' compatibility key)
     bool refs_on_device = false;  // references built by hsddp_build_references for this layout
     bool ref_cols_stale = true;   // Bufs::ref_t behind the reference rows (refreshed by begin_launches)
     // reference-driven MPC state (hsddp_advance): the table's samples on the host (contacts and

@@ -1,8 +1,9 @@
 // hsddp_horizon.cpp — the MPC caller's side of the C-ABI, around the solve: command extraction
 // (HKDMPCSolver::update_foot_placement + publish_mpc_cmd), the receding-horizon shift
 // (HKDProblem::update, HKDProblem.cpp:117-222), the reference table and the per-slot references
-// built from it, hsddp_advance, which steps all of them from the table, and
-// hsddp_restart_elements, which starts single elements again as new problems.  What is here is the
+// built from it, hsddp_advance, which steps all of them from the table,
+// hsddp_restart_elements, which starts single elements again as new problems, and
+// hsddp_copy_elements / _export_ / _import_, which move elements between handles.  What is here is the
 // device and the handle: argument and state checks, allocations, copies, launches,
 // synchronisations, buffer swaps and the handle's flags.  The bookkeeping (which phases, rows,
 // slot maps, strides, pairs and clocks follow) is planned in hsddp_phases.cpp from a read-only
@@ -17,6 +18,7 @@
 #include "hsddp_handle.h"
 #include "hsddp_mpc.h"
 #include "hsddp_restart.h"
+#include "hsddp_elements.h"
 
 using namespace hsddp;
 
@@ -333,6 +335,14 @@ extern "C" int hsddp_shift_elements(hsddp_handle h, int n_steps, const int *cont
     return shift_by_flags(h, n_steps, contact_change, h ? (size_t)n_steps : 0);
 }
 
+// (the hash in the element records' compatibility key, hsddp_elements.h)
+static unsigned long long fnv1a(const void *data, size_t n)
+{
+    unsigned long long h = 1469598103934665603ull;
+    for (size_t i = 0; i < n; ++i) h = (h ^ ((const unsigned char *)data)[i]) * 1099511628211ull;
+    return h;
+}
+
 // ---- batched reference construction ------------------------------------------------------------
 extern "C" int hsddp_set_reference_table(hsddp_handle h, const hsddp_quad_state *table, int n, float dt_ref)
 {
@@ -355,6 +365,7 @@ extern "C" int hsddp_set_reference_table(hsddp_handle h, const hsddp_quad_state 
     h->ref_n = n;
     h->ref_dt = dt_ref;
     h->table_host.assign(table, table + n);
+    h->table_key = fnv1a(table, (size_t)n * sizeof(hsddp_quad_state));
     h->win_start.clear();
     return HSDDP_OK;
 }
@@ -657,6 +668,400 @@ extern "C" int hsddp_restart_elements(hsddp_handle h, const int *mask, const int
     h->meas_held = false;
     if (!x0) h->need_inputs = true;  // as hsddp_advance with x0 = NULL leaves them
     return HSDDP_OK;
+}
+
+// ---- elements moved between slots, handles and host records ----------------------------------------
+// hsddp_copy_elements, hsddp_export_elements, hsddp_import_elements: an element's whole between-tick
+// state copied from a slot of one live handle to a slot of another (or the same), directly or
+// through a host record.  The receiving side is hsddp_restart_elements' machinery (layouts patched
+// in place, repair_pairs, the restride pass, per-element clocks, a compacted list driving the
+// kernels) with the rows read from the source (hsddp_elements.hip) instead of built anew.
+static bool table_driven(hsddp_handle h) { return h->ref_table && !h->win_start.empty() && !h->table_host.empty(); }
+
+static ElementKey key_of(hsddp_handle h)
+{
+    ElementKey k;
+    std::memset(&k, 0, sizeof k);
+    k.Kc = h->p.Kc; k.fp32 = h->p.fp32; k.S_cap = (int)h->S_cap; k.dt = h->desc.dt;
+    k.weights = fnv1a(&h->desc.weights, sizeof h->desc.weights);
+    k.cparams = fnv1a(&h->desc.cparams, sizeof h->desc.cparams);
+    k.has_table = table_driven(h) ? 1 : 0;
+    if (k.has_table) {
+        k.table = h->table_key; k.ref_n = h->ref_n; k.ref_dt = h->ref_dt; k.win_len = h->win_len; k.dt_sim = h->dt_sim;
+    }
+    return k;
+}
+
+// may an element of a handle (or record) with key s continue in a handle with key d?
+static int compatible(const ElementKey &s, const ElementKey &d, bool records)
+{
+    if (s.Kc != d.Kc) return fail(HSDDP_ERR_ARG, "the element's Kc is not the destination's");
+    if (s.dt != d.dt) return fail(HSDDP_ERR_ARG, "the element's dt is not the destination's");
+    if (s.fp32 != d.fp32) return fail(HSDDP_ERR_ARG, "the element's precision mode (riccati_fp32) is not the destination's");
+    if (s.weights != d.weights || s.cparams != d.cparams)
+        return fail(HSDDP_ERR_ARG, "the element's weights or constraint parameters are not the destination's");
+    if (records && s.S_cap != d.S_cap) return fail(HSDDP_ERR_ARG, "the record's size is not the destination's");
+    if (s.has_table != d.has_table)
+        return fail(HSDDP_ERR_UNSUPPORTED, "only one of the two sides drives its references from a table");
+    if (s.has_table && (s.table != d.table || s.ref_n != d.ref_n || s.ref_dt != d.ref_dt || s.win_len != d.win_len ||
+                        s.dt_sim != d.dt_sim))
+        return fail(HSDDP_ERR_UNSUPPORTED, "the two sides' reference tables, window lengths or simulation steps differ");
+    return HSDDP_OK;
+}
+
+// a handle that can give or take an element: a problem uploaded, no inputs pending, the contact rows
+// of the current layout on the host
+static int settled(hsddp_handle h, const char *side)
+{
+    const Params &p = h->p;
+    if (!h->have_problem) return fail(HSDDP_ERR_ARG, std::string(side) + ": upload the problem first");
+    if (h->need_inputs) return fail(HSDDP_ERR_ARG, std::string(side) + ": a shift, advance or restart awaits its inputs");
+    if (!h->contacts_current || h->contacts.size() != (size_t)p.B * (p.P + 1) * 4)
+        return fail(HSDDP_ERR_ARG, std::string(side) + ": no contacts of the current layout on the handle");
+    return HSDDP_OK;
+}
+
+// the handle's host state with the durations only where they are the current layout's
+static HorizonView element_view(hsddp_handle h)
+{
+    HorizonView v = view_of(h);
+    if (h->durations.size() != (size_t)h->p.B * h->p.P * 4) v.durations = nullptr;
+    if (h->win_start.empty()) v.win_start = nullptr;
+    return v;
+}
+
+static ElemSide handle_side(hsddp_handle h, const int *idx)
+{
+    ElemSide s{};
+    s.d = h->d; s.rec = nullptr; s.idx = idx;
+    s.P = h->p.P; s.S = h->p.S; s.hcap = h->p.hcap; s.shared_refs = h->Bref == 1 ? 1 : 0;
+    return s;
+}
+
+static ElemSide record_side(char *base, size_t S_cap)
+{
+    ElemSide s{};
+    s.rec = base; s.idx = nullptr;
+    s.P = HSDDP_MAX_PHASES; s.S = (int)S_cap; s.hcap = REC_HIST; s.shared_refs = 0;
+    return s;
+}
+
+// the solver-info history with room for `need` entries per element, the rows held kept
+static int grow_history(hsddp_handle h, int need)
+{
+    if (need <= h->p.hcap) return HSDDP_OK;
+    const size_t B = h->p.B, old = h->p.hcap;
+    float *nh = nullptr;
+    if (hipMalloc(&nh, B * need * 4 * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(HSDDP_ERR_ALLOC, "hipMalloc: the solver-info history");
+    }
+    HIPCHK(hipMemsetAsync(nh, 0, B * need * 4 * sizeof(float), h->stream));
+    HIPCHK(hipMemcpy2DAsync(nh, (size_t)need * 16, h->hist, old * 16, old * 16, B, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    hipFree(h->hist);
+    h->bytes += B * ((size_t)need - old) * 4 * sizeof(float);
+    h->hist = nh;
+    h->d.hist = nh;
+    h->p.hcap = need;
+    return HSDDP_OK;
+}
+
+// HSDDP_COPY_TIMING=1: the move kernels' device time (HIP events), summed over a call's launches
+struct MoveTimer {
+    bool on;
+    hipStream_t st;
+    float ms = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    MoveTimer(hipStream_t s) : st(s)
+    {
+        static const bool timing = std::getenv("HSDDP_COPY_TIMING") != nullptr;
+        on = timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    }
+    ~MoveTimer()
+    {
+        for (hipEvent_t e : ev)
+            if (e) hipEventDestroy(e);
+    }
+    void begin() { if (on) hipEventRecord(ev[0], st); }
+    void end()  // (synchronises: a diagnostic)
+    {
+        if (!on) return;
+        float t = 0;
+        hipEventRecord(ev[1], st);
+        if (hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) ms += t;
+    }
+};
+
+// Where the moved elements come from: elements index[m] of a live handle, or host records [n].
+struct MoveSource {
+    hsddp_handle h;
+    const int *index;
+    const char *records;
+};
+
+// Slot dst_index[m] of dst becomes move m's source element.  Check, plan (plan_import_batch), the
+// allocations, then apply and commit as hsddp_restart_elements does.  Order on the device: the
+// sources that a same-handle move also overwrites are staged as records first (all of them when the
+// strides change: the restride pass moves every row), records from the host are staged by their
+// copy; then the restride pass, then the direct moves, then the staged ones.
+static int move_elements(hsddp_handle dst, const MoveSource &src, int n, const int *dst_index, const char *who)
+{
+    if (!dst || (!src.h && !src.records) || n < 0) return fail(HSDDP_ERR_ARG, "null handle or records, or n < 0");
+    if (n > 0 && (!dst_index || (src.h && !src.index))) return fail(HSDDP_ERR_ARG, "null index array");
+    if (n == 0) return HSDDP_OK;  // nothing moves: nothing is launched, nothing changes
+    Params &p = dst->p;
+    const int B = p.B;
+    const RecordLayout R = record_layout(p.Kc, dst->S_cap, p.fp32);
+    int rc;
+    // check: the two sides agree, both are settled, the indices
+    const ElementKey kd = key_of(dst);
+    if (src.h) {
+        if (src.h->desc.device != dst->desc.device) return fail(HSDDP_ERR_ARG, "the two handles are on different devices");
+        if ((rc = compatible(key_of(src.h), kd, false)) || (rc = settled(src.h, "source"))) return rc;
+    }
+    if ((rc = settled(dst, "destination"))) return rc;
+    std::vector<ElementImport> in(n);
+    bool at_init = true;
+    int hist_need = 0;
+    if (src.h) {
+        const HorizonView vs = element_view(src.h);
+        for (int m = 0; m < n; ++m) {
+            if (src.index[m] < 0 || src.index[m] >= vs.B) return fail(HSDDP_ERR_ARG, "source element index out of range");
+            export_element(vs, src.index[m], in[m]);
+        }
+        at_init = src.h->reb_at_init;
+        hist_need = src.h->p.hcap;  // (room for whatever a source element holds)
+    } else {
+        for (int m = 0; m < n; ++m) {
+            RecordHeader hd;
+            std::memcpy(&hd, src.records + (size_t)m * R.bytes, sizeof hd);
+            if (hd.version != RECORD_VERSION) return fail(HSDDP_ERR_ARG, "not an element record of this version");
+            if ((rc = compatible(hd.key, kd, true))) return rc;
+            if (hd.hist_n < 0 || hd.hist_n > REC_HIST) return fail(HSDDP_ERR_ARG, "damaged element record");
+            in[m] = hd.host;
+            at_init = at_init && hd.reb_at_init != 0;
+            hist_need = std::max(hist_need, hd.hist_n);
+        }
+    }
+    if (kd.has_table)
+        for (int m = 0; m < n; ++m)
+            if (in[m].win_start < 0 || in[m].win_start >= dst->ref_n) return fail(HSDDP_ERR_ARG, "an element's window start lies outside the table");
+    if (dst->Bref == 1)
+        return fail(HSDDP_ERR_UNSUPPORTED, "the destination has shared references: an element of its own needs per-element "
+                                           "references (ref_per_element = 1)");
+    // plan: what the arriving elements mean for the batch (strides, layouts, rows, pairs, clocks)
+    const std::vector<int> list(dst_index, dst_index + n);
+    RestartBatch r;
+    std::string why;
+    if ((rc = plan_import_batch(element_view(dst), list, in.data(), r, why))) return fail(rc, why);
+    const bool restride = r.restride, in_place = r.in_place, same = src.h == dst;
+    if (restride && !kd.has_table)
+        return fail(HSDDP_ERR_UNSUPPORTED, "the move changes the destination's strides: its other elements' references "
+                                           "are rebuilt from the table, and it has none");
+    // the moves: staged (through records) or direct
+    std::vector<int> direct, staged;
+    {
+        std::vector<char> is_dst(same ? B : 0, 0);
+        if (same)
+            for (int b : list) is_dst[b] = 1;
+        for (int m = 0; m < n; ++m)
+            ((!src.h || (same && (restride || is_dst[src.index[m]]))) ? staged : direct).push_back(m);
+    }
+    const int nd = (int)direct.size(), ns = (int)staged.size();
+    // allocations: the history's room, the workspace (lists, layout records, staged records)
+    HIPCHK(hipSetDevice(dst->desc.device));
+    if (src.h && !same) HIPCHK(hipStreamSynchronize(src.h->stream));
+    HIPCHK(hipStreamSynchronize(dst->stream));
+    constexpr size_t LW = sizeof(Layout) / sizeof(int);
+    const size_t ni = (size_t)2 * n + (in_place ? (size_t)n * LW : 0), ib = (ni * sizeof(int) + 255) & ~(size_t)255;
+    const size_t wbytes = ib + (size_t)ns * R.bytes;
+    char *buf = nullptr, *temp = nullptr;
+    if (restride) {  // (the restride pass and its references use the handle's scratch)
+        if (hipMalloc((void **)&temp, wbytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(HSDDP_ERR_ALLOC, "hipMalloc: the move's workspace");
+        }
+        buf = temp;
+    } else if ((rc = scratch(dst, wbytes, &buf)))
+        return rc;
+    struct Release {
+        char *p;
+        ~Release() { if (p) hipFree(p); }
+    } release{temp};
+    if ((rc = grow_history(dst, hist_need))) return rc;
+    // lists in move order direct, then staged: destination slot, source element, layout record
+    std::vector<int> host(ni);
+    int *hd_ = host.data(), *hs_ = hd_ + n;
+    Layout *hl = (Layout *)(hs_ + n);
+    for (int j = 0; j < n; ++j) {
+        const int m = j < nd ? direct[j] : staged[j - nd];
+        hd_[j] = list[m];
+        hs_[j] = src.h ? src.index[m] : 0;
+        if (in_place) hl[j] = in[m].L;
+    }
+    int *dd = (int *)buf, *dsrc = dd + n;
+    const Layout *dl = in_place ? (const Layout *)(dsrc + n) : nullptr;
+    char *stage = buf + ib;
+    if ((rc = h2d(dd, host.data(), ni * sizeof(int), dst->stream))) return rc;
+    MoveArgs a{};
+    a.Kc = p.Kc; a.fp32 = p.fp32; a.R = R;
+    MoveTimer timer(dst->stream);
+    // apply: the staged sources first
+    if (!src.h) {
+        for (int j = 0; j < ns; ++j)
+            if ((rc = h2d(stage + (size_t)j * R.bytes, src.records + (size_t)staged[j] * R.bytes, R.bytes, dst->stream))) return rc;
+    } else if (ns) {
+        a.n = ns; a.lay = nullptr;
+        timer.begin();
+        launch_move(a, handle_side(dst, dsrc + nd), record_side(stage, dst->S_cap), dst->stream);
+        HIPCHK(hipGetLastError());
+        timer.end();
+    }
+    std::vector<double> th;  // (read by its copy until the call's last synchronisation)
+    if (restride) {  // the other elements' rows to the new strides (installs per-element layouts)
+        // ... with the stored foot heights [B][P][4], which the shift leaves to the next rollout
+        const size_t Po = p.P;
+        std::vector<double> th_old((size_t)B * Po * 4);
+        if ((rc = d2h(th_old.data(), dst->d.term_h, th_old.size() * sizeof(double)))) return rc;
+        if ((rc = shift_apply(dst, r.stride_plan, false, nullptr, false))) return rc;
+        dst->need_inputs = false;
+        const size_t Pn = p.P;
+        th.assign((size_t)B * Pn * 4, 0.0);
+        for (size_t b = 0; b < (size_t)B; ++b)
+            std::copy_n(&th_old[b * Po * 4], std::min(Po, Pn) * 4, &th[b * Pn * 4]);
+        if ((rc = h2d(dst->d.term_h, th.data(), th.size() * sizeof(double), dst->stream))) return rc;
+    }
+    if (r.one) {
+        adopt_shared_layout(dst, r.plans[0].L, &r.reach_in[0]);
+    } else if (in_place) {
+        for (int m = 0; m < n; ++m) {  // (the device records go with the move's kernel)
+            dst->lays[list[m]] = r.plans[m].L;
+            std::copy_n(&r.reach_in[(size_t)m * HSDDP_MAX_PHASES], HSDDP_MAX_PHASES,
+                        &dst->reach_el[(size_t)list[m] * HSDDP_MAX_PHASES]);
+        }
+        if ((rc = repair_pairs(dst, list))) return rc;
+    } else if (!restride) {
+        if ((rc = set_layouts(dst, r.lays))) return rc;
+        dst->reach_el.swap(r.reach);
+    }
+    // contact rows [B][P + 1][4] and durations [B][P][4]; at a new stride the others' rows have moved
+    if (restride) {
+        dst->contacts.swap(r.contacts);
+        dst->durations.swap(r.durations);
+        if ((rc = h2d((void *)dst->d.contacts, dst->contacts.data(), dst->contacts.size() * sizeof(int), dst->stream))) return rc;
+    } else {
+        const bool dur = dst->durations.size() == (size_t)B * p.P * 4;
+        for (int m = 0; m < n; ++m) {
+            int *c = &dst->contacts[(size_t)list[m] * (p.P + 1) * 4];
+            std::fill_n(c, (p.P + 1) * 4, 0);
+            std::copy_n(r.plans[m].contacts, (r.plans[m].L.P + 1) * 4, c);
+            if (!dur) continue;
+            double *q = &dst->durations[(size_t)list[m] * p.P * 4];
+            std::fill_n(q, p.P * 4, 0.0);
+            std::copy_n(r.plans[m].durations, r.plans[m].L.P * 4, q);
+        }
+    }
+    dst->contacts_current = true;
+    // the windows (at a new stride every element's references are rebuilt; the arriving elements'
+    // rows then replace theirs) and the clocks
+    if (!r.win_start.empty()) dst->win_start = r.win_start;
+    if (restride && (rc = build_refs(dst, dst->win_start.data(), dst->win_len, nullptr, dst->dt_sim, false))) return rc;
+    dst->t_cur = r.t_cur;
+    dst->t_el.swap(r.t_el);
+    // the rows: the direct moves, then the staged ones
+    timer.begin();
+    if (nd) {
+        a.n = nd; a.lay = dl;
+        launch_move(a, handle_side(src.h, dsrc), handle_side(dst, dd), dst->stream);
+    }
+    if (ns) {
+        a.n = ns; a.lay = dl ? dl + nd : nullptr;
+        launch_move(a, record_side(stage, dst->S_cap), handle_side(dst, dd + nd), dst->stream);
+    }
+    HIPCHK(hipGetLastError());
+    timer.end();
+    HIPCHK(hipStreamSynchronize(dst->stream));  // (the pageable host rows above are read until here)
+    if (timer.on)
+        std::fprintf(stderr, "%s kernels ms: %.4f (B %d, moved %d%s%s)\n", who, timer.ms, B, n,
+                     in_place ? ", in place" : restride ? ", new strides" : "", ns && src.h ? ", staged" : "");
+    // what the handle caches of rows and layouts (as a restart leaves it); the ReB rows may now differ
+    // from the initial pair
+    dst->slots_fresh = false;
+    dst->sim_fresh = false;
+    dst->meas_held = false;
+    if (!at_init) {
+        dst->reb_at_init = false;
+        p.reb_uniform = 0;
+    }
+    return HSDDP_OK;
+}
+
+extern "C" int hsddp_copy_elements(hsddp_handle dst, hsddp_handle src, int n, const int *dst_index, const int *src_index)
+{
+    if (!dst || !src) return fail(HSDDP_ERR_ARG, "null handle");
+    return move_elements(dst, MoveSource{src, src_index, nullptr}, n, dst_index, "hsddp_copy_elements");
+}
+
+extern "C" size_t hsddp_element_record_bytes(const struct hsddp_handle_t *h)
+{
+    if (!h) { fail(HSDDP_ERR_ARG, "null handle"); return 0; }
+    return record_layout(h->p.Kc, h->S_cap, h->p.fp32).bytes;
+}
+
+extern "C" int hsddp_export_elements(hsddp_handle h, int n, const int *index, void *records)
+{
+    if (!h || n < 0 || (n > 0 && (!index || !records))) return fail(HSDDP_ERR_ARG, "null argument");
+    if (n == 0) return HSDDP_OK;
+    int rc;
+    if ((rc = settled(h, "source"))) return rc;
+    const Params &p = h->p;
+    for (int m = 0; m < n; ++m)
+        if (index[m] < 0 || index[m] >= p.B) return fail(HSDDP_ERR_ARG, "element index out of range");
+    const RecordLayout R = record_layout(p.Kc, h->S_cap, p.fp32);
+    HIPCHK(hipSetDevice(h->desc.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t ib = ((size_t)n * sizeof(int) + 255) & ~(size_t)255;
+    char *buf;
+    if ((rc = scratch(h, ib + (size_t)n * R.bytes, &buf))) return rc;
+    if ((rc = h2d(buf, index, (size_t)n * sizeof(int), h->stream))) return rc;
+    HIPCHK(hipMemsetAsync(buf + ib, 0, (size_t)n * R.bytes, h->stream));  // (rows past the strides: zero)
+    MoveArgs a{};
+    a.n = n; a.Kc = p.Kc; a.fp32 = p.fp32; a.R = R; a.lay = nullptr;
+    MoveTimer timer(h->stream);
+    timer.begin();
+    launch_move(a, handle_side(h, (const int *)buf), record_side(buf + ib, h->S_cap), h->stream);
+    HIPCHK(hipGetLastError());
+    timer.end();
+    HIPCHK(hipMemcpyAsync(records, buf + ib, (size_t)n * R.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (timer.on) std::fprintf(stderr, "hsddp_export_elements kernels ms: %.4f (B %d, moved %d)\n", timer.ms, p.B, n);
+    // the headers: version, compatibility key, host bookkeeping
+    const HorizonView v = element_view(h);
+    const ElementKey key = key_of(h);
+    for (int m = 0; m < n; ++m) {
+        char *rec = (char *)records + (size_t)m * R.bytes;
+        RecordHeader hd;
+        std::memset(&hd, 0, sizeof hd);
+        hd.version = RECORD_VERSION;
+        hd.key = key;
+        export_element(v, index[m], hd.host);
+        hd.reb_at_init = h->reb_at_init ? 1 : 0;
+        ElemState E;
+        std::memcpy(&E, rec + R.el, sizeof E);
+        hd.hist_n = E.hist_n;
+        std::memcpy(rec, &hd, sizeof hd);
+        if (E.hist_n > REC_HIST) rc = HSDDP_ERR_UNSUPPORTED;
+    }
+    if (rc) return fail(rc, "an element holds more solver-info entries than a record has room for (256)");
+    return HSDDP_OK;
+}
+
+extern "C" int hsddp_import_elements(hsddp_handle h, int n, const int *index, const void *records)
+{
+    if (!h || n < 0 || (n > 0 && (!records || !index))) return fail(HSDDP_ERR_ARG, "null argument");
+    if (n == 0) return HSDDP_OK;
+    return move_elements(h, MoveSource{nullptr, nullptr, (const char *)records}, n, index, "hsddp_import_elements");
 }
 
 extern "C" int hsddp_get_phase_info(hsddp_handle h, int *contacts, double *durations)

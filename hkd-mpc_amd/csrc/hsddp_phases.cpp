@@ -476,14 +476,22 @@ void put_restart_rows(const RestartPlan &plan, int P, int *contacts, double *dur
     std::copy_n(plan.durations, plan.L.P * 4, durations);
 }
 
+namespace {
+// The batch's side of the listed elements taking the layouts, rows and reach flags of r.plans /
+// r.reach_in, window starts start[m] and clocks clock[m].  fresh: new problems (a restart: no phase
+// at its end, the clocks at 0, the slot maps of the new references); else elements that arrive as
+// they stood elsewhere (hsddp_copy_elements / hsddp_import_elements).
+int finish_batch(const HorizonView &v, const std::vector<int> &list, const int *start, const float *clock, bool fresh,
+                 RestartBatch &r, std::string &why);
+}  // namespace
+
 int plan_restart_batch(const HorizonView &v, const std::vector<int> &list, const int *window_start,
                        float plan_duration, float dt_mpc, RestartBatch &r, std::string &why)
 {
-    const int B = v.B, n = (int)list.size();
-    const bool elem = v.lays != nullptr;
+    const int n = (int)list.size();
     r = RestartBatch{};
-    r.all = n == B;
     r.plans.resize(n);
+    std::vector<int> start(n);
     for (int m = 0; m < n; ++m) {
         if (v.Bref == 1 && window_start[list[m]] != window_start[0]) {
             why = "shared references hold one window: every window start must be the same";
@@ -492,7 +500,62 @@ int plan_restart_batch(const HorizonView &v, const std::vector<int> &list, const
         if (int rc = plan_restart(v.table, v.ref_n, window_start[list[m]], v.win_len, v.ref_dt, plan_duration,
                                   v.dt_sim, dt_mpc, v.Kc, r.plans[m], why))
             return rc;
+        start[m] = window_start[list[m]];
     }
+    r.reach_in.assign((size_t)n * MAXP, 0);
+    const std::vector<float> clock(n, 0.f);
+    return finish_batch(v, list, start.data(), clock.data(), true, r, why);
+}
+
+void export_element(const HorizonView &v, int b, ElementImport &out)
+{
+    out = ElementImport{};
+    const Layout &L = v.layout(b);
+    out.L = L;
+    std::copy_n(v.reach_of(b), L.P, out.reach);
+    std::copy_n(&v.contacts[(size_t)b * (v.P + 1) * 4], (L.P + 1) * 4, out.contacts);
+    if (v.durations) std::copy_n(&v.durations[(size_t)b * v.P * 4], L.P * 4, out.durations);
+    out.win_start = v.win_start ? v.win_start[v.Bref == 1 ? 0 : b] : 0;
+    out.clock = v.t_el ? v.t_el[b] : v.t_cur;
+}
+
+int plan_import_batch(const HorizonView &v, const std::vector<int> &list, const ElementImport *in, RestartBatch &r,
+                      std::string &why)
+{
+    const int n = (int)list.size();
+    r = RestartBatch{};
+    r.plans.resize(n);
+    r.reach_in.assign((size_t)n * MAXP, 0);
+    std::vector<int> start(n), seen(v.B, 0);
+    std::vector<float> clock(n);
+    for (int m = 0; m < n; ++m) {
+        if (list[m] < 0 || list[m] >= v.B) { why = "element index out of range"; return HSDDP_ERR_ARG; }
+        if (seen[list[m]]++) { why = "a destination element is named twice"; return HSDDP_ERR_ARG; }
+        const Layout &L = in[m].L;
+        Layout chk;
+        if (L.P < 1 || L.P > MAXP || build_layout(L.P, L.N, L.ss, chk, why) || std::memcmp(&chk, &L, sizeof(Layout)) ||
+            control_slots(L) != v.Kc) {
+            why = "an element's layout is not one of the handle's Kc control slots";
+            return HSDDP_ERR_ARG;
+        }
+        r.plans[m].L = L;
+        std::copy_n(in[m].contacts, (MAXP + 1) * 4, r.plans[m].contacts);
+        std::copy_n(in[m].durations, MAXP * 4, r.plans[m].durations);
+        for (int i = 0; i < L.P; ++i) r.reach_in[(size_t)m * MAXP + i] = in[m].reach[i] ? 1 : 0;
+        start[m] = in[m].win_start;
+        clock[m] = in[m].clock;
+    }
+    return finish_batch(v, list, start.data(), clock.data(), false, r, why);
+}
+
+namespace {
+int finish_batch(const HorizonView &v, const std::vector<int> &list, const int *start, const float *clock, bool fresh,
+                 RestartBatch &r, std::string &why)
+{
+    const int B = v.B, n = (int)list.size();
+    const bool elem = v.lays != nullptr;
+    r.all = n == B;
+    auto reach_in = [&](int m) { return &r.reach_in[(size_t)m * MAXP]; };
     // The batch's largest P and S after the restart (the strides of the per-phase and per-slot
     // buffers).  Unlisted elements keep theirs, so the old strides stand unless a new layout exceeds
     // them or a listed element alone held them; only then is every element looked at.
@@ -517,15 +580,20 @@ int plan_restart_batch(const HorizonView &v, const std::vector<int> &list, const
                 }
         }
     }
-    if ((size_t)r.Sn > v.S_cap) { why = "restarted layout exceeds the handle's capacity"; return HSDDP_ERR_ARG; }
-    // one layout for the batch stays (or becomes) the shared one: every element restarted onto one
-    // layout, or some elements of a shared-layout batch restarted onto that layout with no phase of
-    // it at its end.  (Elements with per-element layouts that come to agree stay per element.)
+    if ((size_t)r.Sn > v.S_cap) {
+        why = fresh ? "restarted layout exceeds the handle's capacity" : "an element's layout exceeds the handle's capacity";
+        return HSDDP_ERR_ARG;
+    }
+    // one layout for the batch stays (or becomes) the shared one: every element listed, onto one
+    // layout with one set of reach flags (a restart's: none), or some elements of a shared-layout
+    // batch onto that layout with its flags.  (Elements with per-element layouts that come to agree
+    // stay per element.)
     r.one = true;
-    for (int m = 1; m < n && r.one; ++m) r.one = !std::memcmp(&r.plans[m].L, &r.plans[0].L, sizeof(Layout));
+    for (int m = 1; m < n && r.one; ++m)
+        r.one = !std::memcmp(&r.plans[m].L, &r.plans[0].L, sizeof(Layout)) && std::equal(reach_in(m), reach_in(m) + MAXP, reach_in(0));
     if (!r.all)
         r.one = r.one && !elem && !std::memcmp(&r.plans[0].L, v.shared, sizeof(Layout)) &&
-                std::all_of(v.reach, v.reach + v.shared->P, [](int f) { return f == 0; });
+                std::equal(v.reach, v.reach + v.shared->P, reach_in(0));
     r.restride = r.Pn != v.P || r.Sn != v.S;
     // in place: the strides stand and the layouts are per element already, so the listed elements'
     // layout records, sweep pairs and table rows are patched and nothing of size B is built
@@ -540,7 +608,8 @@ int plan_restart_batch(const HorizonView &v, const std::vector<int> &list, const
         for (int b = 0; b < B; ++b) {
             const bool is = listed[b] >= 0;
             const Layout &L = is ? r.plans[listed[b]].L : v.layout(b);
-            std::vector<int> key = is ? layout_key(L, false) : shift_key(L, v.reach_of(b), 0, nullptr);
+            std::vector<int> key = !is ? shift_key(L, v.reach_of(b), 0, nullptr)
+                                   : fresh ? layout_key(L, false) : shift_key(L, reach_in(listed[b]), 0, nullptr);
             key.push_back(is ? -2 : -3);
             const int seen = keys.size();
             plan.map_id[b] = keys(std::move(key));
@@ -549,7 +618,7 @@ int plan_restart_batch(const HorizonView &v, const std::vector<int> &list, const
             if (is) {
                 for (int i = 0; i < L.P; ++i) {
                     ShiftPhase f;
-                    f.N = L.N[i]; f.ss = L.ss[i]; f.reach = 0;
+                    f.N = L.N[i]; f.ss = L.ss[i]; f.reach = reach_in(listed[b])[i];
                     f.xs.assign(f.N + 1, -1); f.us.assign(f.N, -1); f.rs.assign(f.N, -1);
                     ph.push_back(f);
                 }
@@ -570,14 +639,18 @@ int plan_restart_batch(const HorizonView &v, const std::vector<int> &list, const
             } else {
                 const int Pb = v.layout(b).P;
                 std::copy_n(&v.contacts[(size_t)b * (v.P + 1) * 4], (Pb + 1) * 4, c);
-                std::copy_n(&v.durations[(size_t)b * v.P * 4], Pb * 4, d);
+                if (v.durations) std::copy_n(&v.durations[(size_t)b * v.P * 4], Pb * 4, d);
             }
         }
     } else if (!r.one && !r.in_place) {  // every element's layout and reach flags after the restart
         r.lays.resize(B);
         r.reach.assign((size_t)B * MAXP, 0);
         for (int b = 0; b < B; ++b) {
-            if (listed[b] >= 0) { r.lays[b] = r.plans[listed[b]].L; continue; }
+            if (listed[b] >= 0) {
+                r.lays[b] = r.plans[listed[b]].L;
+                std::copy_n(reach_in(listed[b]), MAXP, &r.reach[(size_t)b * MAXP]);
+                continue;
+            }
             r.lays[b] = v.layout(b);
             std::copy(v.reach_of(b), v.reach_of(b) + r.lays[b].P, &r.reach[(size_t)b * MAXP]);
         }
@@ -588,18 +661,26 @@ int plan_restart_batch(const HorizonView &v, const std::vector<int> &list, const
     r.start.resize(n);
     for (int m = 0; m < n; ++m) {
         std::copy_n(r.plans[m].contacts, (r.plans[m].L.P + 1) * 4, &r.rows[(size_t)m * (P + 1) * 4]);
-        r.map_id[m] = r.slots.add(r.plans[m].L, nullptr, v.dt_sim, v.ref_dt, v.win_len - 1, r.Sn);
-        r.start[m] = window_start[list[m]];
+        if (fresh) r.map_id[m] = r.slots.add(r.plans[m].L, nullptr, v.dt_sim, v.ref_dt, v.win_len - 1, r.Sn);
+        r.start[m] = start[m];
     }
-    r.win_start.assign(v.win_start, v.win_start + v.Bref);
-    for (int m = 0; m < n; ++m) r.win_start[v.Bref == 1 ? 0 : list[m]] = window_start[list[m]];
-    // the clocks: QuadReference's t_cur restarts for the listed elements
-    if (!r.all) {
+    if (v.win_start) {
+        r.win_start.assign(v.win_start, v.win_start + v.Bref);
+        for (int m = 0; m < n; ++m) r.win_start[v.Bref == 1 ? 0 : list[m]] = start[m];
+    }
+    // the clocks: QuadReference's t_cur restarts for the elements of a restart; an element that
+    // arrives keeps its own, and the batch keeps one clock while every element agrees with it
+    bool same = true;
+    for (int m = 1; m < n; ++m) same = same && clock[m] == clock[0];
+    r.t_cur = r.all && same ? clock[0] : v.t_cur;
+    const bool shared = r.all ? same : !fresh && !v.t_el && same && clock[0] == v.t_cur;
+    if (!shared) {
         r.t_el = v.t_el ? std::vector<float>(v.t_el, v.t_el + B) : std::vector<float>(B, v.t_cur);
-        for (int b : list) r.t_el[b] = 0;
+        for (int m = 0; m < n; ++m) r.t_el[list[m]] = clock[m];
     }
     return HSDDP_OK;
 }
+}  // namespace
 
 // ---- sweep pairs -----------------------------------------------------------------------------------
 namespace {

@@ -3,11 +3,11 @@
 // HKDProblem::initialization's segmentation of a reference window (:15-68; hsddp_plan_phases),
 // QuadReference's sample rounding, and on top of them the plans of the MPC caller's entry points:
 // the shift's slot maps, hsddp_advance's walk over the reference table, the references' slot
-// samples, hsddp_restart_elements' batch decisions and the sweep's pairing of equal layouts.  The
-// entry points (hsddp_horizon.cpp, hsddp_api.cpp) check, call a plan here, apply it on the device
-// and commit it to the handle.  No HIP header, no handle and no global state: the handle's host
+// samples, hsddp_restart_elements' and hsddp_copy_elements' batch decisions and the sweep's pairing
+// of equal layouts.  The entry points (hsddp_horizon.cpp, hsddp_api.cpp) check, call a plan here,
+// apply it on the device and commit it to the handle.  No HIP header, no handle and no global state: the handle's host
 // fields are read through a HorizonView, and a plain C++ compiler builds hsddp_phases.cpp on its
-// own (tests/drivers/phases_check.cpp, restart_check.cpp, horizon_check.cpp).
+// own (tests/drivers/phases_check.cpp, restart_check.cpp, horizon_check.cpp, elements_check.cpp).
 #pragma once
 
 #include <cstddef>
@@ -239,13 +239,39 @@ struct RestartBatch {
     SlotMaps slots;         // one per distinct new layout, Sn wide
     std::vector<int> map_id, start;  // [n] each listed element's slot map and window start
     std::vector<int> win_start;      // [Bref] after the restart
-    std::vector<float> t_el;         // the clocks after the restart (empty: shared, at 0)
+    std::vector<float> t_el;         // the clocks after the restart (empty: shared, at t_cur)
+    float t_cur = 0;                 // the batch's shared clock after it (a restart of every element: 0)
+    std::vector<int> reach_in;       // [n][MAXP] the listed elements' reach flags (a restart: none)
 };
 // Refused: differing window starts under shared references, what plan_restart refuses, S past S_cap.
 int plan_restart_batch(const HorizonView &v, const std::vector<int> &list, const int *window_start,
                        float plan_duration, float dt_mpc, RestartBatch &r, std::string &why);
 // one listed element's new rows at stride P: contacts [P + 1][4] and durations [P][4], zero past its phases
 void put_restart_rows(const RestartPlan &plan, int P, int *contacts, double *durations);
+
+// ---- hsddp_copy_elements / hsddp_import_elements ---------------------------------------------------
+// What the host holds of one element between ticks, as an element record carries it: layout, reach
+// flags, contact rows 0 .. P, contact durations (zero without a reference table), window start and
+// QuadReference clock.  Rows past the element's phases are zero.
+struct ElementImport {
+    Layout L;
+    int reach[MAXP];
+    int contacts[(MAXP + 1) * 4];
+    double durations[MAXP * 4];
+    int win_start;
+    float clock;
+};
+// element b of the view
+void export_element(const HorizonView &v, int b, ElementImport &out);
+// The batch's side of slot list[m] becoming the element in[m]: plan_restart_batch's decisions (one,
+// restride, in_place, strides, contact and duration rows, window starts; patch_pairs follows as
+// there) with each listed element's layout, reach flags, rows, window start and clock taken from
+// in[m] instead of a segmentation.  No slot maps (the reference rows arrive with the element).  The
+// batch keeps one clock while every element's equals it, else it moves to per-element clocks.
+// Refused: an index outside the batch or named twice, a layout that is not one of Kc control slots,
+// S past S_cap.
+int plan_import_batch(const HorizonView &v, const std::vector<int> &list, const ElementImport *in, RestartBatch &r,
+                      std::string &why);
 
 // ---- sweep pairs -----------------------------------------------------------------------------------
 // Two elements of equal layout (layout_key with ss) per wave: pairs [n_pairs][2], -1 for no partner,

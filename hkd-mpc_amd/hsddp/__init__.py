@@ -526,6 +526,51 @@ class Solver:
         self._contacts = None
         check(rc)
 
+    # -- elements moved between batches (hsddp_copy_elements / _export_ / _import_) --------------
+    def _follow_strides(self) -> None:
+        P, S = C.c_int(), C.c_int()  # (the strides alone: no walk over the B layouts)
+        check(lib().hsddp_get_strides(self._h, C.byref(P), C.byref(S)))
+        self.P, self.S = P.value, S.value
+        self._contacts = None
+
+    @staticmethod
+    def _index(a) -> np.ndarray:
+        return np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
+
+    def copy_elements(self, src: "Solver", dst_index, src_index) -> None:
+        """Slot dst_index[m] of this batch becomes element src_index[m] of `src` (another Solver on
+        the same device, or this one) as it stood before the call (hsddp_copy_elements): its
+        trajectories, constraint and solver state, inputs, references, layout, window and clock —
+        everything the robot carries between ticks; every other element keeps all it holds.  A
+        source may repeat (fan-out) and a slot may be both source and destination."""
+        di, si = self._index(dst_index), self._index(src_index)
+        if di.shape != si.shape:
+            raise HSDDPError(f"dst_index / src_index: shapes {di.shape} / {si.shape}")
+        rc = lib().hsddp_copy_elements(self._h, src._h, int(di.size), ip(di), ip(si))
+        self._follow_strides()
+        check(rc)
+
+    def element_record_bytes(self) -> int:
+        return int(lib().hsddp_element_record_bytes(self._h))
+
+    def export_elements(self, index) -> np.ndarray:
+        """The records of elements index[m] (hsddp_export_elements): a uint8 array [n][record bytes]
+        that import_elements of a compatible Solver, on any device, takes."""
+        ix = self._index(index)
+        out = np.zeros((ix.size, self.element_record_bytes()), np.uint8)
+        check(lib().hsddp_export_elements(self._h, int(ix.size), ip(ix), out.ctypes.data))
+        return out
+
+    def import_elements(self, index, records) -> None:
+        """Slot index[m] becomes the element of records[m] (hsddp_import_elements)."""
+        ix = self._index(index)
+        rec = np.ascontiguousarray(records, dtype=np.uint8)
+        if rec.size != ix.size * self.element_record_bytes():
+            raise HSDDPError(f"records: {rec.size} bytes, expected {ix.size} x {self.element_record_bytes()}")
+        rc = lib().hsddp_import_elements(self._h, int(ix.size), ip(ix), rec.ctypes.data)
+        self._follow_strides()
+        check(rc)
+
     # -- policy simulation (hsddp_simulate_policy) ---------------------------------------------
     def simulate_policy(self, x_init=None, n_steps: int = 1, n_samples: int | None = None,
                         trajectories: bool = False) -> dict:

@@ -126,6 +126,7 @@ EXPORTS = [
     "hsddp_simulate_policy", "hsddp_update_problem_simulated",
     "hsddp_hkd_state", "hsddp_update_problem_measured", "hsddp_extract_commands_measured",
     "hsddp_restart_elements", "hsddp_set_element_budgets", "hsddp_get_strides",
+    "hsddp_copy_elements", "hsddp_element_record_bytes", "hsddp_export_elements", "hsddp_import_elements",
 ]
 
 
@@ -217,6 +218,15 @@ def lib():
         L.hsddp_restart_elements.argtypes = [V, IP, IP, C.c_float, C.c_float, DP]
         L.hsddp_set_element_budgets.argtypes = [V, IP, IP]
         L.hsddp_get_strides.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "hsddp_copy_elements"):  # (older A/B builds lack the element moves)
+        L.hsddp_copy_elements.argtypes = [V, V, C.c_int, IP, IP]
+        L.hsddp_copy_elements.restype = C.c_int
+        L.hsddp_element_record_bytes.argtypes = [V]
+        L.hsddp_element_record_bytes.restype = C.c_size_t
+        L.hsddp_export_elements.argtypes = [V, C.c_int, IP, V]
+        L.hsddp_export_elements.restype = C.c_int
+        L.hsddp_import_elements.argtypes = [V, C.c_int, IP, V]
+        L.hsddp_import_elements.restype = C.c_int
     _lib = L
     return L
 

@@ -97,3 +97,26 @@ RICCATI_FMA_PER_KNOT = {
     "G = Qx - Qux_c^T k": 24 * 12,
 }
 RICCATI_FLOP_PER_KNOT = 2 * sum(RICCATI_FMA_PER_KNOT.values())
+
+
+def element_move_bytes(S: int, Kc: int, P: int, fp32: bool = False, coincide: bool = True, hist_n: int = 0,
+                       in_place: bool = True) -> dict:
+    """Bytes read and written in HBM per element moved from one handle's slot to another's
+    (hsddp_copy_elements, hsddp_elements.hip): S, P the strides both handles hold
+    the element at, coincide: its nominal and working rows are one buffer's (the working X and U
+    rows are then not moved a second time), hist_n: solver-info entries held, in_place: the
+    destination has per-element layouts and takes the element's layout record (written only)."""
+    d = 8
+    f = 4 if fp32 else 8
+    traj = 1 if coincide else 2                                   # Xbar (+ X), Ubar (+ U)
+    slot = (traj + 2) * NX * d                                    # ... Defect, dX
+    slot += (24 + 24 + 12) * d                                    # ref_x, ref_u, ref_foot
+    slot += 3 * d + 4                                             # slot_cost, slot_feas, slot_viol, slot_div
+    slot += NX * 4 if fp32 else 0                                 # the fp32 Defect copy
+    knot = KCW * f + (traj + 2) * NX * d                          # gains, Ubar (+ U), dU, du
+    knot += 2 * 20 * d + 12 * d + 4                               # ReB delta, eps; cf_u, cf_flag
+    phase = 4 * 4 + 2 * 4 * 4 * d + 4 * d                         # td_mask, al_sigma, al_lambda [4][4]; term_h
+    elem = 160 + 4 + NX * d + (P + 1) * 4 * 4 + hist_n * 4 * 4    # ElemState, sel, x0, contact rows, history
+    read = S * slot + Kc * knot + P * phase + elem
+    written = read + S * (24 + 24 + 12) * d + (272 if in_place else 0)  # the entry-major reference columns
+    return {"read": read, "written": written, "total": read + written}

@@ -30,6 +30,7 @@
  *   hsddp_advance / hsddp_get_phase_info      HKDProblem::update from the reference table   HKDProblem.cpp:117-222
  *   hsddp_restart_elements                    HKDProblem::initialization for some elements of a live batch
  *                                             (HKDMPCSolver::initialize beside ::update)  HKDProblem.cpp:15-111; HKDMPC.cpp:20-94
+ *   hsddp_copy_elements / _export_ / _import_ (no counterpart: one HKDMPCSolver object per robot needs no move)
  *   hsddp_shift / hsddp_update_problem        HKDProblem::update + HKDMPCSolver::update's re-solve
  *                                             setup (warm start reused)  HKDProblem.cpp:117-222; HKDMPC.cpp:96-143
  *   hsddp_set_layout                          a caller-side HKDProblem::update's layout + SinglePhase::
@@ -446,6 +447,74 @@ int hsddp_advance(hsddp_handle h, int n_steps, float plan_duration, float dt_mpc
  * layout on the handle (a shift still awaiting them).  A refused call leaves the handle unchanged. */
 int hsddp_restart_elements(hsddp_handle h, const int *mask, const int *window_start, float plan_duration,
                            float dt_mpc, const double *x0);
+
+/* A robot moved between live batches: for m = 0 .. n - 1, slot dst_index[m] of dst becomes element
+ * src_index[m] of src as it stood before the call, such that the robot cannot tell: its next ticks
+ * equal, bit for bit, the ones it would have run where it was (given the same x0).  dst == src is
+ * allowed, a source may be named several times (fan-out), a slot may be both a source and a
+ * destination; every source is read before any destination is written, and the source is only read
+ * (its buffer selectors are not normalised).  The uses: a robot joins a running batch, a batch is
+ * compacted after robots left, a shard is rebalanced, one robot's state is fanned out over many
+ * slots, a batch grows (create the larger handle with any placeholder problem, copy every robot over).
+ * What moves is everything the robot carries from one call to the next:
+ *   trajectories    the nominal Xbar, Ubar and the 12 compact gain rows per knot (K32 on an fp32
+ *                   handle), the working X, U, Defect, the search direction dX, dU, du; the
+ *                   destination's buffer selector reproduces whether the nominal and working rows
+ *                   coincide (the trial buffer is scratch and is not copied)
+ *   constraints     per-knot ReB (delta, eps); per phase the HSDDP_MAX_TD touchdown slots: mask with
+ *                   its stale / pending bits, sigma, lambda, the stored foot heights; the stored GRF
+ *                   forces and their flags
+ *   solver state    the per-element state behind hsddp_download_element_info (with the flags of the
+ *                   stored constraint values), the solver-info history rows (the destination's
+ *                   capacity grows to the source's), the per-slot sums
+ *   inputs          x0; the contact rows on the host and on the device
+ *   references      the reference rows and their entry-major columns (a source with shared
+ *                   references gives its one row set)
+ *   bookkeeping     the layout, the is_phase_reach_end flags, the phases' contact durations, the
+ *                   window start and the QuadReference clock.  If that clock differs from the one the
+ *                   destination's batch shares, the destination moves to per-element clocks, as
+ *                   hsddp_restart_elements does.
+ * What does not move: hsddp_options and the per-element budgets (they belong to the destination's
+ * slots); the LQ and terminal records and the value export, which the next solve rewrites, so
+ * hsddp_download_lq / _terminal / _value of a moved slot are valid again after it; retry scratch; a
+ * simulation held and the measured foot placements, which the destination drops as a restart does.
+ * Every other element of dst keeps every bit it had.  slots_fresh is cleared on the destination, and
+ * it reads the per-knot ReB rows again once a source's have left the initial pair.
+ * Layouts and strides follow hsddp_restart_elements: a shared-layout destination moves to
+ * per-element layouts unless every element ends on one layout (with one set of reach flags); a move
+ * that changes the batch's largest P or S takes the one restride pass (the other elements'
+ * references are rebuilt from the table); otherwise the work follows n, on the host and on the
+ * device: layout records, pairs and table rows are patched in place, and n = 0 launches nothing.
+ * Between distinct handles the rows are copied directly on dst's stream after src's has been
+ * synchronised; within one handle the sources that are also destinations are staged in the
+ * handle's scratch first.  HSDDP_COPY_TIMING=1 prints the device time of the call's kernels (HIP
+ * events) to stderr.
+ * A refusal leaves both handles unchanged.  HSDDP_ERR_ARG: a NULL handle or index array, n < 0; the
+ * handles are on different devices; Kc, dt, riccati_fp32, weights or cparams differ; either handle
+ * has no problem uploaded or awaits inputs after a shift, advance or restart, or has no contacts of
+ * the current layout; an index out of range, a destination index named twice; a layout's S beyond
+ * the destination's capacity.  HSDDP_ERR_UNSUPPORTED: the destination has shared references
+ * (ref_per_element = 0); only one of the handles drives its references from a table, or both do and
+ * the tables (sample count, dt_ref, samples), window lengths or dt_sim differ; a move that changes
+ * the strides of a destination without a table.  HSDDP_ERR_ALLOC: the workspace or the history's
+ * room could not be allocated (before any write). */
+int hsddp_copy_elements(hsddp_handle dst, hsddp_handle src, int n, const int *dst_index, const int *src_index);
+/* The same state through caller-owned host memory: fixed-size opaque records of
+ * hsddp_element_record_bytes(h) bytes each (it depends on Kc, the state-slot capacity Kc +
+ * HSDDP_MAX_PHASES and the precision mode; a NULL handle: 0, with hsddp_last_error set; it reads the
+ * handle only, hence the const pointer to hsddp_handle's struct).  A record starts with a version word
+ * and the compatibility key of hsddp_copy_elements (Kc, dt, precision, hashes of the weights, the
+ * constraint parameters and the reference table, the table's sizes), then holds the host
+ * bookkeeping and the device rows.  hsddp_export_elements writes the records of elements index[0 ..
+ * n - 1] (an index may repeat) and changes nothing of the handle; HSDDP_ERR_UNSUPPORTED when an
+ * element holds more than 256 solver-info entries.  hsddp_import_elements is hsddp_copy_elements
+ * with record m as the source of slot index[m]: the same rules and codes, a record of another
+ * version or an incompatible handle refused with HSDDP_ERR_ARG / HSDDP_ERR_UNSUPPORTED as there.
+ * Export on one device and import on another is the cross-GPU move; a checkpoint of a batch is the
+ * export of every element. */
+size_t hsddp_element_record_bytes(const struct hsddp_handle_t *h);
+int hsddp_export_elements(hsddp_handle h, int n, const int *index, void *records);
+int hsddp_import_elements(hsddp_handle h, int n, const int *index, const void *records);
 
 /* MultiPhaseDDP::solve's loop bounds per element: element b runs the reference's loops with
  * max_AL_iter[b] outer iterations (MultiPhaseDDP.cpp:257) of max_DDP_iter[b] inner iterations each
