@@ -43,6 +43,14 @@ GAITS = {
     "pronk": [(1, 1, 1, 1), (0, 0, 0, 0)],
     "jump": [(1, 1, 1, 1), (0, 0, 1, 1), (0, 0, 0, 0), (1, 1, 0, 0), (0, 0, 0, 0), (0, 0, 1, 1),
              (0, 0, 0, 0), (1, 1, 1, 1)],
+    # cycles with one and three legs in stance (make_batch(mixed=True) does not draw them)
+    "crawl": [(0, 1, 1, 1), (1, 0, 1, 1), (1, 1, 0, 1), (1, 1, 1, 0)],
+    "amble": [(1, 1, 0, 1), (1, 0, 0, 1), (1, 0, 1, 1), (1, 0, 1, 0), (1, 1, 1, 0), (0, 1, 1, 0), (0, 1, 1, 1),
+              (0, 1, 0, 1)],
+    "hop": [(1, 1, 1, 1), (1, 0, 0, 0), (0, 0, 0, 0), (0, 1, 0, 0), (1, 1, 1, 1), (0, 0, 1, 0), (0, 0, 0, 0),
+            (0, 0, 0, 1)],
+    # all 16 masks in Gray-code order (bit l = leg l): every switch, the wrap-around too, flips one leg
+    "gray": [tuple(((g ^ (g >> 1)) >> l) & 1 for l in range(4)) for g in range(16)],
 }
 
 _MASK64 = (1 << 64) - 1

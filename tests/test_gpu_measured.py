@@ -65,7 +65,11 @@ def assert_same(a, b, what):
 
 
 # ---- 1. the primitive -----------------------------------------------------------------------------
-PATTERNS = np.array([[1, 1, 1, 1], [0, 0, 0, 0], [1, 0, 0, 1], [0, 1, 1, 0], [1, 0, 0, 0], [0, 0, 1, 0]], np.int32)
+# the six patterns the first records have always cycled through, then the other ten of the 16 masks
+PATTERNS = np.array([[1, 1, 1, 1], [0, 0, 0, 0], [1, 0, 0, 1], [0, 1, 1, 0], [1, 0, 0, 0], [0, 0, 1, 0],
+                     [0, 1, 0, 0], [0, 0, 0, 1], [1, 1, 0, 0], [0, 0, 1, 1], [1, 0, 1, 0], [0, 1, 0, 1],
+                     [0, 1, 1, 1], [1, 0, 1, 1], [1, 1, 0, 1], [1, 1, 1, 0]], np.int32)
+assert len({tuple(r) for r in PATTERNS}) == 16
 
 
 @pytest.mark.parametrize("n", [1, 5, 67])

@@ -21,15 +21,29 @@ import mpc_oracle as M  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
+# crawl, amble, hop and gray on their own layouts of 24 knots: the foot-placement search ("first
+# swing -> stance of leg l") on legs whose neighbours stay down, over up to five phase ends
+ODD_LAYOUTS = [("crawl", 4, 6), ("amble", 8, 3), ("hop", 8, 3), ("gray", 12, 2)]
+
+
 @pytest.mark.parametrize("P,N,mixed,fp32,nsteps", [(4, 3, True, False, 1), (8, 2, True, False, 3),
-                                                     (4, 50, False, False, 1), (6, 4, True, True, 2)])
+                                                     (4, 50, False, False, 1), (6, 4, True, True, 2),
+                                                     (None, None, False, False, 3)],
+                         ids=["4-3-True-False-1", "8-2-True-False-3", "4-50-False-False-1", "6-4-True-True-2",
+                              "odd-mask-layouts"])
 def test_commands_match_oracle(P, N, mixed, fp32, nsteps):
-    B = 37
-    prob = syn.make_batch(B, P, N, "jump" if P == 8 else "trot", mixed=mixed)
+    if P is None:  # per-element layouts of the one- and three-leg cycles (10 knots: past gray's 5th phase)
+        B = 13
+        prob = syn.make_layout_batch((ODD_LAYOUTS * 4)[:B])
+        P = prob["P"]
+    else:
+        B = 37
+        prob = syn.make_batch(B, P, N, "jump" if P == 8 else "trot", mixed=mixed)
+    hzs = prob.get("layouts") or [prob["horizons"]] * B
     s = hsddp.Solver(prob, hsddp.load_settings(no_early_exit=1, max_AL_iter=1, max_DDP_iter=2), riccati_fp32=fp32)
     s.solve()
     tr = s.trajectory()
-    rng = np.random.default_rng(P * N)
+    rng = np.random.default_rng(P * N if N else P)
     dur = rng.uniform(0.1, 0.4, (B, P, 4))
     feet = rng.standard_normal((B, 12)).astype(np.float32)
     cmd = s.extract_commands(nsteps, 3.25, 0.01, dur, feet, 0.75)
@@ -38,7 +52,7 @@ def test_commands_match_oracle(P, N, mixed, fp32, nsteps):
     s.close()
     for b in range(B):
         for variant, d_, f_ in ((cmd, dur[b], feet[b]), (cmd1, dur[0], feet[0])):
-            r = M.mpc_command(tr["Xbar"][b], tr["Ubar"][b], tr["K"][b], prob["contacts"][b], prob["horizons"],
+            r = M.mpc_command(tr["Xbar"][b], tr["Ubar"][b], tr["K"][b], prob["contacts"][b], hzs[b],
                               nsteps, 3.25, 0.01, d_, f_, 0.75)
             g = variant[b]
             for f in ("N_mpcsteps", "mpc_times", "hkd_controls", "des_body_state", "contacts", "statusTimes",
@@ -85,9 +99,12 @@ import oracle_lib as O  # noqa: E402
 from mpc_scenario import Scenario  # noqa: E402
 
 
-def _scenario_batch(B, P, N):
-    names = ["trot", "pace", "bound", "pronk"]
-    gaits = [names[b % 4] for b in range(B)]
+ODD_GAITS = ["crawl", "amble", "hop", "gray"]  # one- and three-leg stance, single- and three-leg touchdowns
+
+
+def _scenario_batch(B, P, N, names=None):
+    names = names or ["trot", "pace", "bound", "pronk"]
+    gaits = [names[b % len(names)] for b in range(B)]
     sc = Scenario(gaits, P, N)
     prob = syn.make_batch(B, P, N, "trot")
     inp = sc.inputs(prob["x0"])
@@ -130,18 +147,23 @@ def test_shift_matches_oracle(steps):
     s.close()
 
 
-@pytest.mark.parametrize("ms,params", [(1, False), (0, False), (1, True)], ids=["1", "0", "1-parameters"])
-def test_mpc_loop_matches_oracle(ms, params):
+@pytest.mark.parametrize("ms,params,names,ticks", [(1, False, None, 9), (0, False, None, 9), (1, True, None, 9),
+                                                   (1, False, ODD_GAITS, 12)],
+                         ids=["1", "0", "1-parameters", "1-odd-masks"])
+def test_mpc_loop_matches_oracle(ms, params, names, ticks):
     """HKDMPCSolver::update's loop (HKDMPC.cpp:96-165): shift one step, new inputs with the warm
     start kept, re-solve with max_AL_iter = 2, max_DDP_iter = 1 (quirk A17) — including the
     updates whose new last phase has no shooting states — against the oracle doing the same; with
     multiple (MS 1) and single (MS 0) shooting.  The "parameters" variant runs on
     solver_params.CPARAMS with the ReB / AL schedule on (update_ReB 7, update_relax 0.1,
     update_penalty 3): pushed-back knots and newly registered touchdown constraints start from
-    non-default initial parameters while the shifted ones carry moved values."""
+    non-default initial parameters while the shifted ones carry moved values.  The "odd-masks"
+    variant runs crawl, amble, hop and gray elements for 12 ticks: windows whose phases stand on one
+    and on three legs, touchdown constraints of a single leg and of three legs at once (hop's
+    0100 -> 1111, td_mask 13) registered at the horizon end and carried to the front."""
     import solver_params as SP
     B, P, N = 8, 4, 5
-    sc, prob = _scenario_batch(B, P, N)
+    sc, prob = _scenario_batch(B, P, N, names)
     sched = dict(SP.SCHEDULE) if params else {}
     cpd = SP.CPARAMS if params else None
     s = hsddp.Solver(prob, hsddp.load_settings(MS=ms, **sched), cparams=SP.hsddp_cparams() if params else None)
@@ -152,9 +174,10 @@ def test_mpc_loop_matches_oracle(ms, params):
     kw = dict(max_AL_iter=2, max_DDP_iter=1, MS=ms, **sched)
     s.set_options(hsddp.load_settings(**kw))
     tails = n_td = 0
+    td_seen = set()
     op, _ = O.default_problem(prob["horizons"], prob["dt"], cpd)  # the initial ReB / AL parameters
     moved = lam_moved = 0
-    for it in range(9):
+    for it in range(ticks):
         lay0 = s.layout()
         flags = sc.step(1)
         lay = s.shift(flags)
@@ -184,6 +207,7 @@ def test_mpc_loop_matches_oracle(ms, params):
         dc = s.constraint_params()
         assert np.array_equal(dc["td_mask"], r["td_mask"]), it
         n_td = max(n_td, int((dc["td_mask"] != 0).sum(axis=2).max()))
+        td_seen |= set(dc["td_mask"].reshape(-1).tolist())
         for f in ("al_sigma", "al_lambda", "reb_delta", "reb_eps"):
             assert _rel(dc[f], r[f]) < 1e-9, (it, f)
         for f in ("Xbar", "Ubar", "X", "K"):
@@ -193,6 +217,8 @@ def test_mpc_loop_matches_oracle(ms, params):
     assert tails >= 2  # the loop passed through last phases without shooting states
     assert n_td >= 1   # (phases carrying two touchdown constraints: test_gpu_reference.py's file-driven loop)
     assert (moved >= 1 and lam_moved >= 1) or not params
+    if names is ODD_GAITS:  # a single-leg touchdown constraint and the three-leg one (legs 0, 2, 3)
+        assert td_seen & {1, 2, 4, 8} and 13 in td_seen, sorted(td_seen)
     s.close()
 
 

@@ -87,7 +87,7 @@ def _terminal_plugins_match_the_oracle(c, seed, weights=None):
     assert _close(t["Phix"], r["Phix"]) and _close(t["Phixx"], r["Phixx"])
 
 
-TERMINAL_CASES = [((1, 0, 0, 1), 5), ((1, 1, 1, 1), 6), ((0, 0, 0, 0), 7)]
+TERMINAL_CASES = [((1, 0, 0, 1), 5), ((1, 1, 1, 1), 6), ((0, 0, 0, 0), 7), ((0, 1, 1, 1), 10), ((0, 0, 0, 1), 11)]
 
 
 @pytest.mark.gpu
@@ -102,14 +102,20 @@ def test_terminal_plugins_match_the_oracle_at_nondefault_weights(c, seed):
     _terminal_plugins_match_the_oracle(c, seed, SP.WEIGHTS)
 
 
-def _touchdown_plugin_matches_foot_kinematics(ground):
-    c, cn = (1, 0, 0, 1), (1, 1, 1, 1)    # legs 1 and 2 touch down
+TOUCHDOWN_PAIR = ((1, 0, 0, 1), (1, 1, 1, 1), (1, 2))    # legs 1 and 2 touch down
+# a single leg between stance neighbours; three legs at once (the rows follow the legs' order)
+TOUCHDOWN_ODD = [((1, 1, 0, 1), (1, 1, 1, 1), (2,)), ((0, 1, 0, 0), (1, 1, 1, 1), (0, 2, 3))]
+
+
+def _touchdown_plugin_matches_foot_kinematics(ground, c=TOUCHDOWN_PAIR[0], cn=TOUCHDOWN_PAIR[1], legs=TOUCHDOWN_PAIR[2]):
+    assert legs == tuple(l for l in range(4) if not c[l] and cn[l])
     x = _state(c, 11)
     h, hx = model.touchdown_constraint(x, c, cn, ground=ground)
-    for row, leg in enumerate((1, 2)):
+    for row, leg in enumerate(legs):
         hr, hxr = _height_and_grad(x, leg)
         assert _close(h[0, row], hr - ground, 1e-13) and _close(hx[0, row], hxr, 1e-13)
-    assert np.all(h[0, 2:] == 0) and np.all(hx[0, 2:] == 0)
+    n = len(legs)
+    assert np.all(h[0, n:] == 0) and np.all(hx[0, n:] == 0)
 
 
 @pytest.mark.gpu
@@ -120,3 +126,10 @@ def test_touchdown_plugin_matches_foot_kinematics():
 @pytest.mark.gpu
 def test_touchdown_plugin_matches_foot_kinematics_above_the_ground():
     _touchdown_plugin_matches_foot_kinematics(SP.CPARAMS["ground_height"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ground", [0.0, SP.CPARAMS["ground_height"]])
+@pytest.mark.parametrize("c,cn,legs", TOUCHDOWN_ODD)
+def test_touchdown_plugin_on_one_and_three_legs(c, cn, legs, ground):
+    _touchdown_plugin_matches_foot_kinematics(ground, c, cn, legs)

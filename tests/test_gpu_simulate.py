@@ -126,6 +126,27 @@ def test_per_element_layouts_match_helper(n):
     check(g, ref, ref2, n, "layouts")
 
 
+@pytest.mark.parametrize("n", [7, 24])
+def test_odd_mask_layouts_match_helper(n):
+    """crawl, amble, hop and gray on their own layouts: friction margins over one and three stance
+    legs (min_grf), the gain rows of stance and swing legs side by side within a leg triple, reset
+    maps where one leg lifts as another lands, and touchdown heights of a single leg and of three
+    legs at once (max_td).  n = 7: one knot past crawl's first phase end; 24: the whole horizon."""
+    prob = syn.make_layout_batch([("crawl", 4, 6), ("amble", 8, 3), ("hop", 8, 3), ("gray", 12, 2)])
+    c = prob["contacts"]
+    assert {int(r.sum()) for r in c[0, :5]} == {3} and {1, 3} <= {int(r.sum()) for r in c[3, :13]}
+    d = np.diff(c[2, :9], axis=0)
+    assert np.any((d == 1).sum(axis=1) == 1) and np.any((d == 1).sum(axis=1) == 3)  # hop's touchdowns
+    s, tr = solved(prob)
+    x = perturbed(tr["Xbar"][:, 0], 5, seed=26)
+    ref = R.simulate(prob, tr, x, n)
+    ref2 = R.simulate(prob, tr, x * (1 + 1e-15), n)
+    assert np.all(ref["status"] == 0)
+    g = flat(s.simulate_policy(x, n, trajectories=True))
+    s.close()
+    check(g, ref, ref2, n, "odd masks")
+
+
 # ---- 3. fp32 handle: the downloaded (widened) gains ---------------------------------------------
 def test_fp32_handle_matches_helper():
     prob = syn.make_batch(2, 3, 4, "trot")

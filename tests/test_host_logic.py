@@ -70,7 +70,8 @@ def test_default_options_are_hsddp_option_defaults():
     assert (o.max_DDP_iter, o.max_AL_iter, o.merit_offset) == (3, 2, 10)
 
 
-@pytest.mark.parametrize("gait,P,N", [("trot", 4, 50), ("jump", 8, 25)])
+@pytest.mark.parametrize("gait,P,N", [("trot", 4, 50), ("jump", 8, 25), ("crawl", 4, 4), ("amble", 8, 4),
+                                      ("hop", 8, 4), ("gray", 16, 4)])
 def test_synthetic_batch_layout(gait, P, N):
     prob = syn.make_batch(5, P, N, gait)
     S, Kc = prob["S"], prob["Kc"]
@@ -88,12 +89,43 @@ def test_synthetic_batch_layout(gait, P, N):
     # seeded splitmix64: the same element always gets the same x0
     again = syn.make_batch(2, P, N, gait)
     assert np.array_equal(again["x0"], prob["x0"][:2])
+    # the reference shares m g over the stance legs of each knot's contact (one and three included)
+    for s in (0, N + 1):
+        c = prob["contacts"][0, s // (N + 1)]
+        fz = prob["ref_u"][0, s, 2:12:3]
+        assert np.array_equal(fz != 0, c != 0)
+        assert c.sum() == 0 or np.allclose(fz[c != 0], syn.MASS * syn.GRAVITY / c.sum(), rtol=1e-15)
+    if gait == "gray":
+        rows = [tuple(r) for r in prob["contacts"][0]]
+        assert len(set(rows[:16])) == 16 and rows[16] == rows[0]
+        assert np.all(np.abs(np.diff(prob["contacts"][0], axis=0)).sum(axis=1) == 1)  # the wrap-around too
+        assert [sum(c << l for l, c in enumerate(r)) for r in rows[:4]] == [0, 1, 3, 2]  # bit l = leg l
+        assert set(syn.make_batch(16, 4, 10, mixed=True)["gaits"]) <= {"trot", "pace", "bound", "pronk", "jump"}
+
+
+def test_one_and_three_leg_cycles():
+    """The cycles as the contact-mask tests rely on them: crawl keeps three legs down, amble holds
+    both trot masks between three-leg masks, hop touches down on one leg and on three at once."""
+    assert all(sum(c) == 3 for c in syn.GAITS["crawl"]) and len(set(syn.GAITS["crawl"])) == 4
+    am = syn.GAITS["amble"]
+    for trot in syn.GAITS["trot"]:
+        i = am.index(trot)
+        assert sum(am[i - 1]) == 3 and sum(am[(i + 1) % 8]) == 3
+    hop = syn.GAITS["hop"]
+    assert sorted(sum(c) for c in hop) == [0, 0, 1, 1, 1, 1, 4, 4]
+    td = [tuple(int(b > a) for a, b in zip(hop[i], hop[(i + 1) % 8])) for i in range(8)]
+    assert {(1, 0, 1, 1), (1, 1, 1, 0), (0, 1, 0, 0), (0, 0, 0, 1)} <= set(td)
+    assert all(len(c) == 4 and set(c) <= {0, 1} for cyc in syn.GAITS.values() for c in cyc)
 
 
 def test_mixed_batch_has_per_element_reference():
     prob = syn.make_batch(16, 4, 10, mixed=True)
     assert prob["ref_x"].shape[0] == 16
     assert len(set(prob["gaits"])) > 1
+    # the draw stays on the five gaits the benchmark and the older tests were written for
+    old = {"trot", "pace", "bound", "pronk", "jump"}
+    assert set(prob["gaits"]) <= old
+    assert set(syn.make_batch(64, 4, 10, mixed=True, jump_layout=True)["gaits"]) == old
 
 
 def test_splitmix64_known_values():

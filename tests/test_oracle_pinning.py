@@ -50,7 +50,7 @@ def _refs(contact):
 
 
 CASES = [((1, 0, 0, 1), (0, 1, 1, 0), 1), ((1, 1, 1, 1), (1, 1, 1, 1), 2), ((0, 0, 0, 0), (0, 0, 0, 0), 3),
-         ((1, 1, 0, 0), (0, 0, 1, 1), 4)]
+         ((1, 1, 0, 0), (0, 0, 1, 1), 4), ((1, 1, 0, 1), (1, 0, 1, 1), 8), ((0, 0, 1, 0), (0, 1, 1, 1), 9)]
 
 
 def _fd(f, z, h):
@@ -86,7 +86,8 @@ def test_running_derivatives_are_derivatives_of_the_cost(c, cn, seed):
     assert np.allclose(r["B"], B_fd, rtol=1e-6, atol=1e-9)
 
 
-@pytest.mark.parametrize("c,seed", [((1, 0, 0, 1), 5), ((1, 1, 1, 1), 6), ((0, 0, 0, 0), 7)])
+@pytest.mark.parametrize("c,seed", [((1, 0, 0, 1), 5), ((1, 1, 1, 1), 6), ((0, 0, 0, 0), 7), ((0, 1, 1, 1), 10),
+                                    ((0, 0, 0, 1), 11)])
 def test_terminal_derivatives_without_touchdown(c, seed):
     """No leg touches down at this phase end (cn = c): Phi is the tracking Qf term plus
     foot_term_cost times the foot regularisation (HKDCost.cpp:39-63), Phix / Phixx its derivatives."""
