@@ -1344,6 +1344,9 @@ __global__ __launch_bounds__(64) void k_riccati_select(Params p, Bufs d)
         if (reg > 1e2) break;
         if (d.retry_flag[f * p.retry_m + a - 1] == 1) { win = a; break; }
     }
+    // every attempt of a full schedule failed: the loop's exit value is the next mu, the first past
+    // 1e2 (retry_m is the longest schedule, so that step is the one the sequential loop stops on)
+    if (!win && reg <= 1e2) reg = fmax(reg * p.update_regularization, 1e-03);
     real *Ko = Prec<real>::K(d) + b * p.Kc * KCW;
     double *dUo = d.dU + b * p.Kc * NX;
     if (win) {

@@ -198,8 +198,11 @@ def test_full_batch_properties():
     assert np.all(info["iters"] == 3)
     assert np.mean(info["cost"] < c0) > 0.99
     assert st.n_backward_launches == 3
-    # spot-check a strided sample of elements against the oracle
-    sample = list(range(0, B, 512))
+    # spot-check a sample of elements against the oracle: the strided eight (all even, so each the
+    # first half-wave of its sweep pair and lane group 0 of its k_decide wave), then odd elements at
+    # every residue mod 4 and the last element (every element: test_gpu_batch_sizes.py)
+    sample = list(range(0, B, 512)) + [1, 1027, 2046, 3073, B - 1]
+    assert {b % 4 for b in sample} == {0, 1, 2, 3} and sum(b % 2 for b in sample) >= 4
     r = O.solve_batch(prob, O.default_options(no_early_exit=1, max_AL_iter=1, max_DDP_iter=3),
                       n_threads=8, elements=sample)
     assert rel(tr["Xbar"][sample], r["Xbar"]) < 1e-9
