@@ -232,6 +232,8 @@ extern "C" int hsddp_destroy(hsddp_handle h)
     for (hipEvent_t e : h->iter_done)
         if (e) hipEventDestroy(e);
     if (h->host_counter) hipHostFree(h->host_counter);
+    if (h->terrain_pin) hipHostFree(h->terrain_pin);
+    if (h->terrain_up) hipEventDestroy(h->terrain_up);
     if (h->copy_stream) hipStreamSynchronize(h->copy_stream);
     for (int q = 0; q < 2; ++q) {
         if (h->cmd_dev[q]) hipFree(h->cmd_dev[q]);
@@ -399,6 +401,7 @@ extern "C" int hsddp_set_element_layouts(hsddp_handle h, const int *n_phases, co
     }
     if ((rc = set_layouts(h, lays))) return rc;
     h->reach_el.assign((size_t)B * HSDDP_MAX_PHASES, 0);  // HKDProblem.cpp:56-57 (quirk A15)
+    h->terrain.clear();       // (the phases it described are gone)
     h->have_problem = false;  // inputs of the new layouts next (hsddp_upload_problem)
     h->sim_fresh = false;
     h->contacts_current = false;
@@ -463,6 +466,7 @@ extern "C" int hsddp_set_layout(hsddp_handle h, int n_phases, const int *horizon
     int reach[HSDDP_MAX_PHASES];
     for (int i = 0; i < n_phases; ++i) reach[i] = reach_end && reach_end[i] ? 1 : 0;
     adopt_shared_layout(h, L, reach);
+    h->terrain.clear();       // (the phases it described are gone)
     h->have_problem = false;  // inputs of the new layout next (hsddp_upload_problem)
     h->sim_fresh = false;
     h->need_inputs = false;
@@ -732,7 +736,8 @@ extern "C" int hsddp_simulate_policy(hsddp_handle h, int n_samples, int n_steps,
         HIPCHK(hipEventCreate(&ev[1]));
         HIPCHK(hipEventRecord(ev[0], h->stream));
     }
-    launch_simulate_policy(p, h->d, a, h->stream);
+    if ((rc = sync_terrain(h))) return rc;
+    launch_simulate_policy(p, h->d, a, terrain_of(h), h->stream);
     HIPCHK(hipGetLastError());
     if (timing) {
         float ms = 0;
@@ -895,15 +900,16 @@ extern "C" int hsddp_download_constraint_values(hsddp_handle h, double *grf_g, d
                 for (int k = 0; k < L.N[i]; ++k) {
                     const size_t q = b * Kc + L.k0[i] + k;
                     const double *f = (el[b].ovr && cff[q]) ? &cfu[q * 12] : &U[q * NX];
+                    const double mu = h->terrain.empty() ? p.mu : h->terrain[(b * P + i) * 2];
                     for (int l = 0; l < 4; ++l) {
                         if (!h->contacts[(b * (P + 1) + i) * 4 + l]) continue;
                         const double *fl = f + 3 * l;
                         double *g = grf_g + q * 20 + 5 * l;  // GRFConstraint rows (HKDConstraints.cpp:15-22)
                         g[0] = fl[2];
-                        g[1] = -fl[0] + p.mu * fl[2];
-                        g[2] = fl[0] + p.mu * fl[2];
-                        g[3] = -fl[1] + p.mu * fl[2];
-                        g[4] = fl[1] + p.mu * fl[2];
+                        g[1] = -fl[0] + mu * fl[2];
+                        g[2] = fl[0] + mu * fl[2];
+                        g[3] = -fl[1] + mu * fl[2];
+                        g[4] = fl[1] + mu * fl[2];
                     }
                 }
         }
@@ -922,6 +928,91 @@ extern "C" int hsddp_download_constraint_values(hsddp_handle h, double *grf_g, d
                             ((m >> l) & 1) && !(m & TD_STALE) ? th[(b * P + i) * 4 + l] : 0.0;
                 }
     }
+    return HSDDP_OK;
+}
+
+// ---- per-phase terrain ---------------------------------------------------------------------------
+// The host rows are the source of truth (hsddp_handle.h); the kernels' copy follows by sync_terrain.
+extern "C" int hsddp_set_terrain(hsddp_handle h, const double *mu, const double *ground)
+{
+    if (!h) return fail(HSDDP_ERR_ARG, "null handle");
+    if (!h->have_problem) return fail(HSDDP_ERR_ARG, "upload the problem first");
+    const size_t B = h->p.B, P = h->p.P;
+    const double fill[2] = {h->desc.cparams.mu_fric, h->desc.cparams.ground_height};
+    std::vector<double> rows;
+    if (mu || ground) {
+        rows.resize(B * P * 2);
+        for (size_t b = 0; b < B; ++b) {
+            const size_t Pb = layout_of(h, b).P;
+            for (size_t i = 0; i < P; ++i) {
+                const bool own = i < Pb;  // (rows past the element's phases are not read)
+                const double m = own && mu ? mu[b * P + i] : fill[0], g = own && ground ? ground[b * P + i] : fill[1];
+                if (!std::isfinite(m) || !std::isfinite(g)) return fail(HSDDP_ERR_ARG, "terrain: a value is not finite");
+                if (own && mu && !(m > 0)) return fail(HSDDP_ERR_ARG, "terrain: a friction coefficient is not positive");
+                rows[(b * P + i) * 2] = m;
+                rows[(b * P + i) * 2 + 1] = g;
+            }
+        }
+    }
+    if (!rows.empty())
+        if (int rc = ensure_terrain_table(h)) return rc;
+    // (the iteration graphs are keyed on the table pointer: off and on find their own)
+    h->terrain.swap(rows);
+    h->terrain_stale = true;
+    h->slots_fresh = false;  // the stored slot costs were formed with the old friction coefficients
+    return HSDDP_OK;
+}
+
+extern "C" int hsddp_get_terrain(hsddp_handle h, double *mu, double *ground)
+{
+    if (!h) return fail(HSDDP_ERR_ARG, "null handle");
+    const size_t n = (size_t)h->p.B * h->p.P;
+    for (size_t q = 0; q < n; ++q) {
+        if (mu) mu[q] = h->terrain.empty() ? h->desc.cparams.mu_fric : h->terrain[2 * q];
+        if (ground) ground[q] = h->terrain.empty() ? h->desc.cparams.ground_height : h->terrain[2 * q + 1];
+    }
+    return HSDDP_OK;
+}
+
+int hsddp::ensure_terrain_table(hsddp_handle h)
+{
+    if (h->terrain_dev) return HSDDP_OK;
+    const size_t cap = (size_t)h->p.B * HSDDP_MAX_PHASES * 2;
+    HIPCHK(hipSetDevice(h->desc.device));
+    HIPCHK(hipHostMalloc((void **)&h->terrain_pin, cap * sizeof(double), 0));
+    HIPCHK(hipEventCreateWithFlags(&h->terrain_up, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(h->terrain_up, h->stream));
+    return dalloc(h, h->terrain_dev, cap);
+}
+
+int hsddp::sync_terrain(hsddp_handle h)
+{
+    if (h->terrain.empty() || !h->terrain_stale) return HSDDP_OK;
+    if (!h->terrain_dev) return fail(HSDDP_ERR_DEVICE, "terrain rows without a device table");
+    const size_t bytes = h->terrain.size() * sizeof(double);
+    HIPCHK(hipSetDevice(h->desc.device));
+    HIPCHK(hipEventSynchronize(h->terrain_up));  // (the last upload has read the staging)
+    std::memcpy(h->terrain_pin, h->terrain.data(), bytes);
+    // HSDDP_TERRAIN_TIMING=1: the upload's device time (HIP events) to stderr (a diagnostic)
+    static const bool timing = std::getenv("HSDDP_TERRAIN_TIMING") != nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (timing) {
+        HIPCHK(hipEventCreate(&ev[0]));
+        HIPCHK(hipEventCreate(&ev[1]));
+        HIPCHK(hipEventRecord(ev[0], h->stream));
+    }
+    HIPCHK(hipMemcpyAsync(h->terrain_dev, h->terrain_pin, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(h->terrain_up, h->stream));
+    if (timing) {
+        float ms = 0;
+        HIPCHK(hipEventRecord(ev[1], h->stream));
+        HIPCHK(hipEventSynchronize(ev[1]));
+        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        hipEventDestroy(ev[0]);
+        hipEventDestroy(ev[1]);
+        std::fprintf(stderr, "terrain upload ms: %.4f (%zu bytes)\n", ms, bytes);
+    }
+    h->terrain_stale = false;
     return HSDDP_OK;
 }
 

@@ -41,6 +41,27 @@ template <typename PT>
 DEV double foot_weight(const PT &p, const int *c, int j) { return p.foot_gain * p.foot_w[j % 3] * c[j / 3]; }
 DEV bool touchdown(const int *c, const int *cn, int l) { return c[l] == 0 && cn[l] == 1; }
 
+// ---- per-phase terrain (hsddp_set_terrain) -----------------------------------------------------
+// The kernels that read the friction coefficient or the ground height end in an argument pack:
+// empty — the handle-wide Params::mu / ::ground, the arguments and the code of a handle without
+// terrain — or one pointer to the handle's [B][P] (mu, ground) pairs, read at (element, phase).
+template <bool ON>
+struct TerrT {
+    const double *t;
+    DEV double mu(const Params &p, int b, int i) const
+    {
+        if constexpr (ON) return t[((size_t)b * p.P + i) * 2];
+        else return p.mu;
+    }
+    DEV double ground(const Params &p, int b, int i) const
+    {
+        if constexpr (ON) return t[((size_t)b * p.P + i) * 2 + 1];
+        else return p.ground;
+    }
+};
+DEV TerrT<false> terrain_of() { return {nullptr}; }
+DEV TerrT<true> terrain_of(const double *t) { return {t}; }
+
 // ---- the phase layout of element b ----------------------------------------------------------
 // The handle's layout (Params, read in place: runtime phase indices never index the by-value copy)
 // or, with per-element layouts (Params::elem_layout, hsddp_set_element_layouts), element b's own
@@ -207,8 +228,9 @@ DEV double cost_foot(const Params &p, const int *c, const double *x, const doubl
     }
     return lf;
 }
-// ovr: older control forces of the stored GRF constraint values (constraint_forces), else u's
-DEV double cost_reb(const Params &p, const int *c, const double *u, const double *delta, const double *eps, double &mk,
+// ovr: older control forces of the stored GRF constraint values (constraint_forces), else u's;
+// mu: the friction coefficient of the knot's phase
+DEV double cost_reb(const Params &p, double mu, const int *c, const double *u, const double *delta, const double *eps, double &mk,
                     const double *ovr)
 {
     double rc = 0.0;
@@ -227,7 +249,7 @@ DEV double cost_reb(const Params &p, const int *c, const double *u, const double
                 const double f[3] = {grf_force(u, ovr, 3 * lg), grf_force(u, ovr, 3 * lg + 1), grf_force(u, ovr, 3 * lg + 2)};
 #pragma unroll
                 for (int r = 0; r < 5; ++r) {
-                    const double g = grf_value(p.mu, r, f);
+                    const double g = grf_value(mu, r, f);
                     mk = fmin(mk, g);
                     const double t = (g - 2 * dl) * inv_dl;
                     prod *= g > dl ? g : 1.0;
@@ -242,7 +264,7 @@ DEV double cost_reb(const Params &p, const int *c, const double *u, const double
                 const double f[3] = {grf_force(u, ovr, 3 * lg), grf_force(u, ovr, 3 * lg + 1), grf_force(u, ovr, 3 * lg + 2)};
 #pragma unroll
                 for (int r = 0; r < 5; ++r) {
-                    double g = grf_value(p.mu, r, f);
+                    double g = grf_value(mu, r, f);
                     mk = fmin(mk, g);
                     rc += eps[5 * lg + r] * reb_cost(g, delta[5 * lg + r], log(delta[5 * lg + r]));
                 }
@@ -266,7 +288,7 @@ DEV double cost_combine(const Params &p, const int *c, double lt, double lu, dou
 }
 
 // running cost l_k (tracking + foot regularisation + dt * ReB), and min(0, min g)
-DEV double running_cost(const Params &p, const int *c, const double *x, const double *u, const double *xr,
+DEV double running_cost(const Params &p, double mu, const int *c, const double *x, const double *u, const double *xr,
                         const double *ur, const double *pf, const double *delta, const double *eps, double &viol,
                         const double *ovr = nullptr)
 {
@@ -289,7 +311,7 @@ DEV double running_cost(const Params &p, const int *c, const double *x, const do
     }
     const double lt = cost_tracking(p, c, x, xrv), lu = cost_control(p, u, urv), lf = cost_foot(p, c, x, xrv, pfv);
     double mk;
-    const double rc = cost_reb(p, c, u, delta, eps, mk, ovr);
+    const double rc = cost_reb(p, mu, c, u, delta, eps, mk, ovr);
     viol = mk;
     return cost_combine(p, c, lt, lu, lf, rc);
 }
@@ -370,15 +392,15 @@ DEV double terminal_cost_h(const Params &p, const int *c, const double *x, const
     return phi;
 }
 
-// terminal cost Phi (tracking Qf + 10 * foot + AL), max |h| and h per constraint leg (stored:
-// terminal_cost_h)
-DEV double terminal_cost(const Params &p, const int *c, const double *x, const double *xr, const double *pf,
+// terminal cost Phi (tracking Qf + 10 * foot + AL), max |h| and h per constraint leg above the
+// phase's ground height (stored: terminal_cost_h)
+DEV double terminal_cost(const Params &p, double ground, const int *c, const double *x, const double *xr, const double *pf,
                          const int *mask, const double *sig, const double *lam, double &tviol, double *h_out,
                          bool stored)
 {
     const unsigned u = td_union(mask);
 #pragma unroll
-    for (int l = 0; l < 4; ++l) h_out[l] = ((u >> l) & 1) ? hkd_foot_height_grad(l, x, nullptr) - p.ground : 0.0;
+    for (int l = 0; l < 4; ++l) h_out[l] = ((u >> l) & 1) ? hkd_foot_height_grad(l, x, nullptr) - ground : 0.0;
     return terminal_cost_h(p, c, x, xr, pf, mask, sig, lam, h_out, tviol, stored);
 }
 

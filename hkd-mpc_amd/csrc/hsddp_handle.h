@@ -50,6 +50,7 @@ struct hsddp_handle_t {
         Bufs d;
         double alpha = 0;
         const int *budget = nullptr;
+        const double *terrain = nullptr;
         int par = 0;  // which host count slot (host_counter[8 + 4 * par + 1]) its copy fills
     } iter_graph[8];
     int iter_graph_next = 0;
@@ -142,6 +143,16 @@ struct hsddp_handle_t {
     hsddp_robot_state *meas_states = nullptr;
     float *meas_feet = nullptr;
     bool meas_held = false;
+    // per-phase terrain (hsddp_set_terrain): the host rows [B][P][2] = (mu, ground) at the stride
+    // p.P, rows past an element's phases at the cparams pair — the source of truth, moved with the
+    // phases by hsddp_phases.cpp; empty: terrain off.  The device copy the terrain instantiations
+    // read ([B][HSDDP_MAX_PHASES] pairs allocated on first use, so the pointer the iteration graphs
+    // freeze never moves) is uploaded from pinned staging when the host rows changed (sync_terrain);
+    // terrain_up: that upload's event (the staging is rewritten only after it)
+    std::vector<double> terrain;
+    double *terrain_dev = nullptr, *terrain_pin = nullptr;
+    bool terrain_stale = false;
+    hipEvent_t terrain_up = nullptr;
 };
 
 namespace hsddp {
@@ -188,6 +199,8 @@ inline HorizonView view_of(hsddp_handle h)
     v.win_start = h->win_start.data(); v.win_len = h->win_len; v.dt_sim = h->dt_sim;
     v.t_cur = h->t_cur;
     v.t_el = h->t_el.empty() ? nullptr : h->t_el.data();
+    v.terrain = h->terrain.empty() ? nullptr : h->terrain.data();
+    v.fill[0] = h->desc.cparams.mu_fric; v.fill[1] = h->desc.cparams.ground_height;
     return v;
 }
 
@@ -195,6 +208,16 @@ inline HorizonView view_of(hsddp_handle h)
 inline const int *budget_of(hsddp_handle h) { return h->budgets_on ? h->budgets : nullptr; }
 inline int outer_bound(hsddp_handle h) { return h->budgets_on ? h->bud_AL : h->opt.max_AL_iter; }
 inline int inner_bound(hsddp_handle h) { return h->budgets_on ? h->bud_DDP : h->opt.max_DDP_iter; }
+
+// the table the kernels' terrain instantiations read (null: terrain off, the plain instantiations).
+// Whoever turns terrain on allocates the table first (ensure_terrain_table), so host rows never go
+// with a null table — which would launch the plain instantiations on a handle with terrain.
+inline const double *terrain_of(hsddp_handle h) { return h->terrain.empty() ? nullptr : h->terrain_dev; }
+// hsddp_api.cpp: the device table, its pinned staging and the upload's event (allocated once)
+int ensure_terrain_table(hsddp_handle h);
+// ... and the table brought up to the host rows on the handle's stream (before the launches of a
+// call that reads it; never inside a graph capture)
+int sync_terrain(hsddp_handle h);
 
 // phase of control slot kc in a layout
 inline int phase_of_control(const Layout &L, int kc)

@@ -203,6 +203,9 @@ static int shift_apply(hsddp_handle h, const ShiftPlan &plan, bool defer, int *o
     int rc;
     if ((rc = flatten_shift(plan, p.Kc, h->S_cap, m, why))) return fail(rc, why);
     const int Snew = m.S_new, Pnew = m.P_new;
+    // the terrain rows follow the phases on the host (the old rows are read before the layouts change)
+    std::vector<double> terrain;
+    if (!h->terrain.empty()) shift_terrain(view_of(h), plan, Pnew, terrain);
     std::vector<int> &smap = m.smap, &cmap = m.cmap, &rmap = m.rmap, &pmap = m.pmap, &nadd = m.nadd;
     HIPCHK(hipSetDevice(h->desc.device));
     Bufs &d = h->d;
@@ -293,6 +296,10 @@ static int shift_apply(hsddp_handle h, const ShiftPlan &plan, bool defer, int *o
         shifted_layouts(plan, lays, reach);
         if ((rc = set_layouts(h, lays))) return rc;
         h->reach_el.swap(reach);
+    }
+    if (!h->terrain.empty()) {
+        h->terrain.swap(terrain);
+        h->terrain_stale = true;
     }
     h->need_inputs = true;
     h->refs_on_device = false;  // built for the old layout
@@ -600,6 +607,11 @@ extern "C" int hsddp_restart_elements(hsddp_handle h, const int *mask, const int
                              &h->durations[(size_t)list[m] * p.P * 4]);
     }
     h->contacts_current = true;
+    if (!h->terrain.empty()) {  // a new problem's terrain is the handle's cparams, as on a new handle
+        const HorizonView v = view_of(h);
+        for (int m = 0; m < n; ++m) put_terrain_rows(nullptr, 0, p.P, v.fill, &h->terrain[(size_t)list[m] * p.P * 2]);
+        h->terrain_stale = true;
+    }
     if (restride && (rc = h2d((void *)h->d.contacts, h->contacts.data(), h->contacts.size() * sizeof(int), h->stream)))
         return rc;
     // the window starts; references: at a new stride every element's are rebuilt; shared ones (every
@@ -856,6 +868,18 @@ static int move_elements(hsddp_handle dst, const MoveSource &src, int n, const i
     std::string why;
     if ((rc = plan_import_batch(element_view(dst), list, in.data(), r, why))) return fail(rc, why);
     const bool restride = r.restride, in_place = r.in_place, same = src.h == dst;
+    // an arriving element's terrain rows pass hsddp_set_terrain's checks (a record is outside input)
+    bool brings_terrain = false;
+    for (int m = 0; m < n; ++m) {
+        if (!in[m].has_terrain) continue;
+        brings_terrain = true;
+        for (int i = 0; i < in[m].L.P; ++i) {
+            const double mu = in[m].terrain[2 * i], ground = in[m].terrain[2 * i + 1];
+            if (!std::isfinite(mu) || !std::isfinite(ground) || !(mu > 0))
+                return fail(HSDDP_ERR_ARG, "an element's terrain rows hold a non-finite value or a friction coefficient <= 0");
+        }
+    }
+    if (brings_terrain && (rc = ensure_terrain_table(dst))) return rc;
     if (restride && !kd.has_table)
         return fail(HSDDP_ERR_UNSUPPORTED, "the move changes the destination's strides: its other elements' references "
                                            "are rebuilt from the table, and it has none");
@@ -963,6 +987,21 @@ static int move_elements(hsddp_handle dst, const MoveSource &src, int n, const i
         }
     }
     dst->contacts_current = true;
+    // the terrain rows arrive with the elements (a source without terrain: cparams rows); a
+    // destination without terrain takes it up when an element brings some
+    {
+        const HorizonView v = view_of(dst);
+        if (brings_terrain && dst->terrain.empty()) {
+            dst->terrain.resize((size_t)B * p.P * 2);
+            for (int b = 0; b < B; ++b) put_terrain_rows(nullptr, 0, p.P, v.fill, &dst->terrain[(size_t)b * p.P * 2]);
+        }
+        if (!dst->terrain.empty()) {
+            for (int m = 0; m < n; ++m)
+                put_terrain_rows(in[m].has_terrain ? in[m].terrain : nullptr, in[m].L.P, p.P, v.fill,
+                                 &dst->terrain[(size_t)list[m] * p.P * 2]);
+            dst->terrain_stale = true;
+        }
+    }
     // the windows (at a new stride every element's references are rebuilt; the arriving elements'
     // rows then replace theirs) and the clocks
     if (!r.win_start.empty()) dst->win_start = r.win_start;

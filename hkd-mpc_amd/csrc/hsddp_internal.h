@@ -210,21 +210,25 @@ struct Bufs {
 };
 
 // kernel launchers (hsddp_kernels.hip)
+// terrain: the per-phase (mu, ground) pairs [B][P] (hsddp_set_terrain; the terrain instantiations),
+// or null: Params::mu / ::ground for every phase, the instantiations and arguments without terrain.
+// Not in Bufs: the kernels that never read it (the sweep, the linear rollout, the shift, ...) keep
+// their argument segments
 // tix: the trial's index in the inner iteration's line search (-1: the initial rollout)
 // (last: this trial is the search's last step size — used when the rollout launch also decides)
 void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
-                    hipStream_t st);
+                    const double *terrain, hipStream_t st);
 void launch_decide(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
-                   hipStream_t st);
+                   const double *terrain, hipStream_t st);
 // nominal rows of every element into buffer 0 (Bufs::sel bit 0 cleared), for host transfers
 void launch_normalize(const Params &p, const Bufs &d, hipStream_t st);
 // every element's working rows back at its nominal ones (sel), its Defect rows zero
 void launch_reset_working(const Params &p, const Bufs &d, hipStream_t st);
-void launch_lq(const Params &p, const Bufs &d, hipStream_t st);
+void launch_lq(const Params &p, const Bufs &d, const double *terrain, hipStream_t st);
 void launch_riccati(const Params &p, const Bufs &d, hipStream_t st);
 void launch_lin_rollout(const Params &p, const Bufs &d, hipStream_t st);
 void launch_outer_begin(const Params &p, const Bufs &d, const int *budget, hipStream_t st);
-void launch_reb_update(const Params &p, const Bufs &d, hipStream_t st);
+void launch_reb_update(const Params &p, const Bufs &d, const double *terrain, hipStream_t st);
 void launch_outer_end(const Params &p, const Bufs &d, const int *budget, hipStream_t st);
 void launch_reset_elements(const Params &p, const Bufs &d, hipStream_t st);
 void launch_init_params(const Params &p, const Bufs &d, hipStream_t st);

@@ -112,8 +112,8 @@ DEV void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <bool EL>
-DEV void terminal_task(const Params &p, const Bufs &d, TermLds &S, int task, int t)
+template <bool EL, typename TR>
+DEV void terminal_task(const Params &p, const Bufs &d, const TR &terr, TermLds &S, int task, int t)
 {
     const int b = task / p.P, i = task % p.P;
     const ElemState &E = d.el[b];
@@ -178,7 +178,7 @@ DEV void terminal_task(const Params &p, const Bufs &d, TermLds &S, int task, int
 #pragma unroll
             for (int k = 0; k < 3; ++k) shx[l][12 + 3 * l + k] = R.r[2][0] * dpb[0][k] + R.r[2][1] * dpb[1][k] + R.r[2][2] * dpb[2][k];
             shx[l][5] = 1.0;
-            h = (sx[5] + R.r[2][0] * pb[0] + R.r[2][1] * pb[1] + R.r[2][2] * pb[2]) - p.ground;
+            h = (sx[5] + R.r[2][0] * pb[0] + R.r[2][1] * pb[1] + R.r[2][2] * pb[2]) - terr.ground(p, b, i);
             if (!tdc) {  // a reset-map leg without a constraint: no AL gradient
                 h = 0.0;
 #pragma unroll
@@ -293,7 +293,7 @@ DEV void terminal_task(const Params &p, const Bufs &d, TermLds &S, int task, int
 
 // lu + ReB gradient / Hessian of one knot (SinglePhase.cpp:380-394); the GRF constraint values from
 // the control row's forces, or the older ones ovr (constraint_forces)
-DEV void lq_lu_reb(const Params &p, const int *c, const double *u, const double *ovr, const double *ur, const double *dl,
+DEV void lq_lu_reb(const Params &p, double mu, const int *c, const double *u, const double *ovr, const double *ur, const double *dl,
                    const double *ep, double *lu, double *rb)
 {
 #pragma unroll
@@ -313,7 +313,7 @@ DEV void lq_lu_reb(const Params &p, const int *c, const double *u, const double 
 #pragma unroll
             for (int r = 0; r < 5; ++r) {
                 double row[3], d1, d2;
-                grf_row(p.mu, r, row);
+                grf_row(mu, r, row);
                 double g = row[0] * f0 + row[1] * f1 + row[2] * f2;
                 const double dlr = U ? p.grf_delta : dl[5 * lg + r];
                 reb_derivs(g, dlr, U ? inv_du : 1.0 / dlr, d1, d2);
@@ -335,8 +335,8 @@ DEV void lq_lu_reb(const Params &p, const int *c, const double *u, const double 
 
 // One terminal wave: tasks (element, phase) TERM_TPW wave .. + TERM_TPW - 1 on S[0 ..]; the first
 // wave also resets the iteration's counters (k_terminal's comment)
-template <bool EL>
-DEV void terminal_wave(const Params &p, const Bufs &d, TermLds *S, long wave, int lane)
+template <bool EL, typename TR>
+DEV void terminal_wave(const Params &p, const Bufs &d, const TR &terr, TermLds *S, long wave, int lane)
 {
     if (p.retry_cap > 0 && wave == 0 && lane == 0) *d.retry_count = 0;
     if (wave == 0)
@@ -344,7 +344,7 @@ DEV void terminal_wave(const Params &p, const Bufs &d, TermLds *S, long wave, in
     if (wave == 0 && lane < 4) d.counter[lane] = 0;
     const int h = lane / TERM_TL;
     const long task = wave * TERM_TPW + h;
-    if (task < (long)p.B * p.P) terminal_task<EL>(p, d, S[h], (int)task, lane % TERM_TL);
+    if (task < (long)p.B * p.P) terminal_task<EL>(p, d, terr, S[h], (int)task, lane % TERM_TL);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -354,9 +354,11 @@ DEV void terminal_wave(const Params &p, const Bufs &d, TermLds *S, long wave, in
 // The A - I / B pieces go out by direct stores (staging them would keep all 102 values live).
 // SLOTS: the slot costs and |Defect|^2 are recomputed (Params::lq_slots; instantiated apart so the
 // common path keeps the registers the cost code would take)
-template <bool F32, bool EL, bool SLOTS>
-__global__ __launch_bounds__(256, FWD_MINB) void k_lq(Params p, Bufs d)
+// tr: the terrain table, or nothing (TerrT, hsddp_device.h)
+template <bool F32, bool EL, bool SLOTS, typename... TR>
+__global__ __launch_bounds__(256, FWD_MINB) void k_lq(Params p, Bufs d, TR... tr)
 {
+    const auto terr = terrain_of(tr...);
     using T = std::conditional_t<F32, float, double>;
     // the record stage of the knot waves, or the LDS of the terminal waves (blocks after them: small
     // batches, launch_lq)
@@ -371,7 +373,7 @@ __global__ __launch_bounds__(256, FWD_MINB) void k_lq(Params p, Bufs d)
     const long nunit = (long)p.B * (BY_KNOT ? p.Kc : p.S);
     const long nknot = (nunit + 255) / 256;
     if ((long)blockIdx.x >= nknot) {
-        terminal_wave<EL>(p, d, reinterpret_cast<TermLds *>(lds) + w * TERM_TPW, ((long)blockIdx.x - nknot) * 4 + w, lane);
+        terminal_wave<EL>(p, d, terr, reinterpret_cast<TermLds *>(lds) + w * TERM_TPW, ((long)blockIdx.x - nknot) * 4 + w, lane);
         return;
     }
     sridx[w][lane] = -1; // before any early return: lanes without a record stay -1
@@ -423,9 +425,10 @@ __global__ __launch_bounds__(256, FWD_MINB) void k_lq(Params p, Bufs d)
     const double *ovr = constraint_forces(d, E, b, kc);
     const double *ur = ref_ptr(p, d.ref_u, b, s, NU);
     const double *dl = d.reb_delta + ((size_t)b * p.Kc + kc) * 20, *ep = d.reb_eps + ((size_t)b * p.Kc + kc) * 20;
+    const double mu = terr.mu(p, b, i);
     if (SLOTS) {  // the running cost (else the last rollout's: same trajectory, same parameters)
         double viol;
-        d.slot_cost[(size_t)b * p.S + s] = running_cost(p, c, x, u, xr, ur, pf, dl, ep, viol, ovr);
+        d.slot_cost[(size_t)b * p.S + s] = running_cost(p, mu, c, x, u, xr, ur, pf, dl, ep, viol, ovr);
     }
 
     // the record in the solver's Riccati precision (fp64, or fp32 in config C5's mode)
@@ -475,7 +478,7 @@ __global__ __launch_bounds__(256, FWD_MINB) void k_lq(Params p, Bufs d)
     }
     // lu + ReB gradient / Hessian (SinglePhase.cpp:380-394)
     double lu[NU], rb[24];
-    lq_lu_reb(p, c, u, ovr, ur, dl, ep, lu, rb);
+    lq_lu_reb(p, mu, c, u, ovr, ur, dl, ep, lu, rb);
 #pragma unroll
     for (int j = 0; j < NU; ++j) put(LQ_LU + j, lu[j]);
 #pragma unroll
@@ -508,8 +511,8 @@ DEV void finish_defect(const Params &p, const Bufs &d, int b, int s, int k, cons
 
 // the terminal cost of phase i at its last slot s (x = X[N]) with its violation and touchdown
 // residuals; stored: with the constraints' stored residuals (a phase the rollout did not complete),
-// else as a rollout completing the phase computes them
-DEV void finish_terminal(const Params &p, const Bufs &d, int b, int s, int i, const int *c, const int *cn, const double *x,
+// else as a rollout completing the phase computes them; ground: the phase's ground height
+DEV void finish_terminal(const Params &p, const Bufs &d, double ground, int b, int s, int i, const int *c, const int *cn, const double *x,
                          bool stored = false)
 {
     const size_t sb = (size_t)b * p.S;
@@ -517,24 +520,25 @@ DEV void finish_terminal(const Params &p, const Bufs &d, int b, int s, int i, co
     double tv, h[4];
     const size_t q = ((size_t)b * p.P + i) * MTD;
     (void)cn;
-    d.slot_cost[sb + s] = terminal_cost(p, c, x, xr, pf, d.td_mask + q, d.al_sigma + q * 4, d.al_lambda + q * 4, tv, h,
+    d.slot_cost[sb + s] = terminal_cost(p, ground, c, x, xr, pf, d.td_mask + q, d.al_sigma + q * 4, d.al_lambda + q * 4, tv, h,
                                         stored);
     d.slot_viol[sb + s] = tv;
 #pragma unroll
     for (int l = 0; l < 4; ++l) d.term_h[((size_t)b * p.P + i) * 4 + l] = h[l];
 }
 
-// the running cost of control slot kc = k0(i) + k at state slot s; COLS: the reference from the
-// entry-major copy (Bufs::ref_t: lanes on consecutive slots read contiguous pieces)
+// the running cost of control slot kc = k0(i) + k at state slot s, mu its phase's friction
+// coefficient; COLS: the reference from the entry-major copy (Bufs::ref_t: lanes on consecutive slots
+// read contiguous pieces)
 template <bool COLS = false>
-DEV void finish_running(const Params &p, const Bufs &d, int b, int s, int kc, const int *c, const double *x, const double *u)
+DEV void finish_running(const Params &p, const Bufs &d, double mu, int b, int s, int kc, const int *c, const double *x, const double *u)
 {
     if constexpr (COLS) {
         const double *dl = d.reb_delta + ((size_t)b * p.Kc + kc) * 20, *ep = d.reb_eps + ((size_t)b * p.Kc + kc) * 20;
         alignas(16) double xr[NX], ur[NU], pf[12];
         ref_from_cols(p, d, b, s, xr, ur, pf);
         double viol;
-        d.slot_cost[(size_t)b * p.S + s] = running_cost(p, c, x, u, xr, ur, pf, dl, ep, viol);
+        d.slot_cost[(size_t)b * p.S + s] = running_cost(p, mu, c, x, u, xr, ur, pf, dl, ep, viol);
         d.slot_viol[(size_t)b * p.S + s] = viol;
         return;
     }
@@ -543,19 +547,19 @@ DEV void finish_running(const Params &p, const Bufs &d, int b, int s, int kc, co
     const double *ur = ref_ptr(p, d.ref_u, b, s, NU);
     const double *dl = d.reb_delta + ((size_t)b * p.Kc + kc) * 20, *ep = d.reb_eps + ((size_t)b * p.Kc + kc) * 20;
     double viol;
-    d.slot_cost[sb + s] = running_cost(p, c, x, u, xr, ur, pf, dl, ep, viol);
+    d.slot_cost[sb + s] = running_cost(p, mu, c, x, u, xr, ur, pf, dl, ep, viol);
     d.slot_viol[sb + s] = viol;
 }
 
-template <typename L_>
-DEV void finish_slot(const Params &p, const Bufs &d, const L_ &L, int b, int s, int i, int k, const int *c,
+template <typename L_, typename TR>
+DEV void finish_slot(const Params &p, const Bufs &d, const TR &terr, const L_ &L, int b, int s, int i, int k, const int *c,
                      const int *cn, const double *x, const double *xs, const double *u)
 {
     finish_defect(p, d, b, s, k, x, xs);
     if (k == L.N(i))
-        finish_terminal(p, d, b, s, i, c, cn, x);
+        finish_terminal(p, d, terr.ground(p, b, i), b, s, i, c, cn, x);
     else
-        finish_running(p, d, b, s, L.k0(i) + k, c, x, u);
+        finish_running(p, d, terr.mu(p, b, i), b, s, L.k0(i) + k, c, x, u);
 }
 
 // trial tix > 0 of an inner iteration runs only when an element is still searching after trial
@@ -691,8 +695,8 @@ DEV double from_prev_lane(double v)
 // reset map into the phase's first slot (MultiPhaseDDP.cpp:73-81) with that slot's Defect, and the
 // terminal cost at its last slot.  These run in waves of their own: inside the slot waves, a
 // lane's reset map or terminal cost (foot kinematics) stalled its 63 neighbours.
-template <bool EL>
-DEV void rollout_boundary(const Params &p, const Bufs &d, double eps, int init, long t)
+template <bool EL, typename TR>
+DEV void rollout_boundary(const Params &p, const Bufs &d, const TR &terr, double eps, int init, long t)
 {
     if (t >= (long)p.B * p.P) return;
     const int i = (int)(t / p.B), b = (int)(t % p.B);
@@ -722,20 +726,20 @@ DEV void rollout_boundary(const Params &p, const Bufs &d, double eps, int init, 
         finish_defect(p, d, b, s0, 0, x, xs);
     }
     trial(sN, x);
-    finish_terminal(p, d, b, sN, i, c, cn, x);
+    finish_terminal(p, d, terr.ground(p, b, i), b, sN, i, c, cn, x);
 }
 
 // WIDE: p.S >= RW (instantiated apart: a wave's 64 slots then belong to at most two elements, and
 // the kernel carries only that staging path)
-template <bool EL, bool WIDE>
-DEV void rollout_block(const Params &p, const Bufs &d, double eps, int init, int tix)
+template <bool EL, bool WIDE, typename TR>
+DEV void rollout_block(const Params &p, const Bufs &d, const TR &terr, double eps, int init, int tix)
 {
     __shared__ double Xt[RW * RS];
     const int lane = threadIdx.x;
     const long total = (long)p.B * p.S;
     const long nslot = (total + 63) / 64;
     if ((long)blockIdx.x >= nslot) {  // the phase-boundary waves (after the slot waves)
-        rollout_boundary<EL>(p, d, eps, init, ((long)blockIdx.x - nslot) * 64 + lane);
+        rollout_boundary<EL>(p, d, terr, eps, init, ((long)blockIdx.x - nslot) * 64 + lane);
         return;
     }
     // (every second trial walks the slot blocks from the batch's end, where the trial before's last
@@ -816,7 +820,7 @@ DEV void rollout_block(const Params &p, const Bufs &d, double eps, int init, int
         d2 *ug = (d2 *)(kubuf(tb) + kq * NU);
 #pragma unroll
         for (int j = 0; j < NU / 2; ++j) ug[j] = d2{u[2 * j], u[2 * j + 1]};
-        finish_running<true>(p, d, b, s, L.k0(i) + k, c, x, u);
+        finish_running<true>(p, d, terr.mu(p, b, i), b, s, L.k0(i) + k, c, x, u);
     }
     RSTAMP(4);
     // u_prev: the previous slot's control row is the previous lane's (k > 0: slot s - 1 is a
@@ -895,10 +899,11 @@ DEV void rollout_block(const Params &p, const Bufs &d, double eps, int init, int
 // SinglePhase::hybrid_rollout's sequential branch (SinglePhase.cpp:185-222), X[k] = Xsim[k]
 // (X[0] = x_init when the set is empty) and U[k] = Ubar[k] + eps dU[k] + K[k] (X[k] - Xbar[k]),
 // then the slot outputs of those states.  One thread per element; rare (a few states per element).
-template <bool EL>
-__global__ __launch_bounds__(64) void k_rollout_tail(Params p, Bufs d, double eps, int init, int tix)
+template <bool EL, typename... TR>
+__global__ __launch_bounds__(64) void k_rollout_tail(Params p, Bufs d, double eps, int init, int tix, TR... tr)
 {
     if (ls_skip(d, tix)) return;
+    const auto terr = terrain_of(tr...);
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= p.B) return;
     const ElemState &E = d.el[b];
@@ -951,7 +956,7 @@ __global__ __launch_bounds__(64) void k_rollout_tail(Params p, Bufs d, double ep
                 for (int j = 0; j < NU; ++j) { u[j] = add_step(ub[j], eps, du[j]) + u[j]; ug[j] = u[j]; }
                 up = u;
             }
-            finish_slot(p, d, L, b, s, i, k, c, cn, x, xs, up);
+            finish_slot(p, d, terr, L, b, s, i, k, c, cn, x, xs, up);
             if (k < N) hkd_step(x, u, cd, p.dt, xs);
         }
     }
@@ -967,8 +972,8 @@ __global__ __launch_bounds__(64) void k_rollout_tail(Params p, Bufs d, double ep
 // the block's barrier, the phase-start Defects (Xsim[0] = x_init: x0 or the reset map of the
 // previous phase's X[N], MultiPhaseDDP.cpp:73-81) and the phases without shooting states (a new
 // last phase of <= 2 knots after a receding-horizon shift), which start from that reset map.
-template <bool EL>
-DEV void ss_phase(const Params &p, const Bufs &d, int b, int i, double eps, const double *x_init)
+template <bool EL, typename TR>
+DEV void ss_phase(const Params &p, const Bufs &d, const TR &terr, int b, int i, double eps, const double *x_init)
 {
     const auto L = layout_of<EL>(d, b);
     const size_t sb = (size_t)b * p.S, kb = (size_t)b * p.Kc;
@@ -994,7 +999,7 @@ DEV void ss_phase(const Params &p, const Bufs &d, int b, int i, double eps, cons
         for (int j = 0; j < NX; ++j) xg[j] = x[j];
         if (k > 0 || x_init) finish_defect(p, d, b, s, k, x, k > 0 ? xs : x);
         if (k == N) {
-            finish_terminal(p, d, b, s, i, c, cn, x);
+            finish_terminal(p, d, terr.ground(p, b, i), b, s, i, c, cn, x);
             break;
         }
         // U = Ubar + eps dU + K (X - Xbar) (SinglePhase.cpp:200), K from the 12 coupled gain rows
@@ -1011,15 +1016,16 @@ DEV void ss_phase(const Params &p, const Bufs &d, int b, int i, double eps, cons
         }
         double *ug = U + (kb + kc) * NU;
         for (int j = 0; j < NU; ++j) { u[j] = add_step(ub[j], eps, du[j]) + u[j]; ug[j] = u[j]; }
-        finish_running(p, d, b, s, kc, c, x, u);
+        finish_running(p, d, terr.mu(p, b, i), b, s, kc, c, x, u);
         hkd_step(x, u, cd, p.dt, xs);
     }
 }
 
-template <bool EL>
-__global__ __launch_bounds__(64) void k_rollout_ss(Params p, Bufs d, double eps, int init, int tix)
+template <bool EL, typename... TR>
+__global__ __launch_bounds__(64) void k_rollout_ss(Params p, Bufs d, double eps, int init, int tix, TR... tr)
 {
     if (ls_skip(d, tix)) return;
+    const auto terr = terrain_of(tr...);
     const int b = blockIdx.x * 4 + (threadIdx.x >> 4), i = threadIdx.x & 15;
     bool mine = false, shoot = false;
     if (b < p.B) {
@@ -1028,7 +1034,7 @@ __global__ __launch_bounds__(64) void k_rollout_ss(Params p, Bufs d, double eps,
         mine = (init ? !E.done : E.ls_active != 0) && i < L.P();
         shoot = mine && L.ss(i) > 0;
     }
-    if (shoot) ss_phase<EL>(p, d, b, i, eps, nullptr);
+    if (shoot) ss_phase<EL>(p, d, terr, b, i, eps, nullptr);
     __syncthreads();  // every phase's X[N] written (same block)
     if (!mine) return;
     const auto L = layout_of<EL>(d, b);
@@ -1048,7 +1054,7 @@ __global__ __launch_bounds__(64) void k_rollout_ss(Params p, Bufs d, double eps,
         for (int j = 0; j < NX; ++j) x[j] = X[(sb + s0) * NX + j];
         finish_defect(p, d, b, s0, 0, x, xi);
     } else {
-        ss_phase<EL>(p, d, b, i, eps, xi);
+        ss_phase<EL>(p, d, terr, b, i, eps, xi);
     }
 }
 
@@ -1063,8 +1069,8 @@ __global__ __launch_bounds__(64) void k_rollout_ss(Params p, Bufs d, double eps,
 // break now hold the trial's values, the break knot keeps its earlier ones, the later knots are
 // untouched) and recompute the slot outputs from the break knot on.  No cross-lane operation (the
 // caller's lanes diverge).
-template <bool EL>
-DEV void diverged_fixup(const Params &p, const Bufs &d, const LayT<EL> &L, int b, int g, int sbrk)
+template <bool EL, typename TR>
+DEV void diverged_fixup(const Params &p, const Bufs &d, const TR &terr, const LayT<EL> &L, int b, int g, int sbrk)
 {
     int i, ks;
     slot_phase(L, sbrk, i, ks);
@@ -1112,7 +1118,7 @@ DEV void diverged_fixup(const Params &p, const Bufs &d, const LayT<EL> &L, int b
         // kernel's registers; the arithmetic is the slot kernels')
         const double *x = XT + (sb + s) * NX;
         if (k == L.N(ip)) {
-            finish_terminal(p, d, b, s, ip, c, cn, x, true);
+            finish_terminal(p, d, terr.ground(p, b, ip), b, s, ip, c, cn, x, true);
             continue;
         }
         const int kc = L.k0(ip) + k;
@@ -1122,7 +1128,7 @@ DEV void diverged_fixup(const Params &p, const Bufs &d, const LayT<EL> &L, int b
         const double *ur = ref_ptr(p, d.ref_u, b, s, NU);
         const double *dl = d.reb_delta + (kq + kc) * 20, *ep = d.reb_eps + (kq + kc) * 20;
         double viol;
-        d.slot_cost[sb + s] = running_cost(p, c, x, u, xr, ur, pf, dl, ep, viol, ovr);
+        d.slot_cost[sb + s] = running_cost(p, terr.mu(p, b, ip), c, x, u, xr, ur, pf, dl, ep, viol, ovr);
         d.slot_viol[sb + s] = viol;
     }
 }
@@ -1134,8 +1140,8 @@ DEV void diverged_fixup(const Params &p, const Bufs &d, const LayT<EL> &L, int b
 // the 1e6 bound (slot_div) is rejected after its rows and slot outputs are made the reference's
 // mixed ones (diverged_fixup); max_tconstr / max_pconstr then cover the phases before the break
 // only (MultiPhaseDDP.cpp:83-92).
-template <bool EL>
-DEV void decide_group(const Params &p, const Bufs &d, double eps, int last, int init, int tix, int group,
+template <bool EL, typename TR>
+DEV void decide_group(const Params &p, const Bufs &d, const TR &terr, double eps, int last, int init, int tix, int group,
                       const int *budget)
 {
     const int lane = threadIdx.x, g = lane & 15, base = lane & ~15;
@@ -1175,7 +1181,7 @@ DEV void decide_group(const Params &p, const Bufs &d, double eps, int last, int 
     const bool dvg = act && sbrk < NONE;
     int ibrk = NONE;
     if (__builtin_amdgcn_ballot_w64(dvg)) {  // (wave-uniform: the lanes of other elements repeat their sums)
-        if (dvg) diverged_fixup<EL>(p, d, L, b, g, sbrk);
+        if (dvg) diverged_fixup<EL>(p, d, terr, L, b, g, sbrk);
         __threadfence();
         kd = NONE;
         sums();
@@ -1259,12 +1265,12 @@ DEV void decide_group(const Params &p, const Bufs &d, double eps, int last, int 
 }
 
 // (six waves per SIMD as before the divergence path: that rare path spills instead)
-template <bool EL>
+template <bool EL, typename... TR>
 __global__ __launch_bounds__(64) void k_decide(Params p, Bufs d, double eps, int last,
-                                                                                         int init, int tix, const int *budget)
+                                                                                         int init, int tix, const int *budget, TR... tr)
 {
     if (ls_skip(d, tix)) return;
-    decide_group<EL>(p, d, eps, last, init, tix, blockIdx.x, budget);
+    decide_group<EL>(p, d, terrain_of(tr...), eps, last, init, tix, blockIdx.x, budget);
 }
 
 // One line-search trial: the slot and boundary blocks (rollout_block), and — FUSE, small batches
@@ -1272,12 +1278,13 @@ __global__ __launch_bounds__(64) void k_decide(Params p, Bufs d, double eps, int
 // every block publishes its slot outputs (device-scope release) and takes a ticket; the block
 // holding the last ticket (acquire) runs k_decide's work for the batch, four elements at a time,
 // and resets the ticket counter.  One launch less per trial on the latency path of C1.
-template <bool EL, bool FUSE, bool WIDE>
+template <bool EL, bool FUSE, bool WIDE, typename... TR>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HSDDP_ROLLOUT_WAVES))) void k_rollout(
-    Params p, Bufs d, double eps, int init, int tix, int last, const int *budget)
+    Params p, Bufs d, double eps, int init, int tix, int last, const int *budget, TR... tr)
 {
     if (ls_skip(d, tix)) return;
-    rollout_block<EL, WIDE>(p, d, eps, init, tix);
+    const auto terr = terrain_of(tr...);
+    rollout_block<EL, WIDE>(p, d, terr, eps, init, tix);
     if constexpr (FUSE) {
         __shared__ int ticket;
         __threadfence();
@@ -1285,7 +1292,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HSDDP_ROLLOU
         __syncthreads();
         if (ticket != (int)gridDim.x - 1) return;
         __threadfence();
-        for (int q = 0; q < (p.B + 3) / 4; ++q) decide_group<EL>(p, d, eps, last, init, tix, q, budget);
+        for (int q = 0; q < (p.B + 3) / 4; ++q) decide_group<EL>(p, d, terr, eps, last, init, tix, q, budget);
         if (threadIdx.x == 0) d.counter[7] = 0;
     }
 }
@@ -1358,9 +1365,10 @@ __global__ void k_outer_begin(Params p, Bufs d, const int *budget)
 }
 
 // update_REB_params (ConstraintsBase.h:168-183) per (element, control slot)
-template <bool EL>
-__global__ __launch_bounds__(256) void k_reb_update(Params p, Bufs d)
+template <bool EL, typename... TR>
+__global__ __launch_bounds__(256) void k_reb_update(Params p, Bufs d, TR... tr)
 {
+    const auto terr = terrain_of(tr...);
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long)p.B * p.Kc) return;
     const int b = (int)(gid / p.Kc), kc = (int)(gid % p.Kc);
@@ -1375,13 +1383,14 @@ __global__ __launch_bounds__(256) void k_reb_update(Params p, Bufs d)
     // the knot's stored GRF constraint values: from the control row, or older forces
     const double *ovr = constraint_forces(d, d.el[b], b, kc);
     double *dl = d.reb_delta + gid * 20, *ep = d.reb_eps + gid * 20;
+    const double mu = terr.mu(p, b, i);
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
         if (!c[l]) continue;
 #pragma unroll
         for (int r = 0; r < 5; ++r) {
             const double f[3] = {grf_force(u, ovr, 3 * l), grf_force(u, ovr, 3 * l + 1), grf_force(u, ovr, 3 * l + 2)};
-            double g = grf_value(p.mu, r, f);
+            double g = grf_value(mu, r, f);
             if (g > -p.pconstr_thresh) continue;
             ep[5 * l + r] *= p.update_ReB;
             dl[5 * l + r] *= p.update_relax;
@@ -1772,6 +1781,18 @@ static inline unsigned blocks_for(long n, int bs) { return (unsigned)((n + bs - 
         if (p.elem_layout) hipLaunchKernelGGL(kern<true>, grid, block, 0, st, __VA_ARGS__);         \
         else hipLaunchKernelGGL(kern<false>, grid, block, 0, st, __VA_ARGS__);                      \
     } while (0)
+// ... of a kernel that reads the terrain: with the table as its last argument (`terrain`, the
+// launcher's: the handle's table while its terrain is on), else with the arguments as they stand
+#define LAUNCH_TR(kern, grid, block, st, ...)                                                       \
+    do {                                                                                            \
+        if (terrain) hipLaunchKernelGGL(kern, grid, block, 0, st, __VA_ARGS__, terrain);            \
+        else hipLaunchKernelGGL(kern, grid, block, 0, st, __VA_ARGS__);                             \
+    } while (0)
+#define LAUNCH_EL_TR(kern, grid, block, st, ...)                                                    \
+    do {                                                                                            \
+        if (p.elem_layout) LAUNCH_TR(kern<true>, grid, block, st, __VA_ARGS__);                     \
+        else LAUNCH_TR(kern<false>, grid, block, st, __VA_ARGS__);                                  \
+    } while (0)
 
 // small batches without non-shooting tails decide each trial in its rollout launch (k_rollout FUSE);
 // HSDDP_NO_FUSED_DECIDE=1 (read at every launch: a test switches it in-process) keeps k_decide's
@@ -1784,10 +1805,10 @@ static bool fused_decide(const Params &p)
 }
 
 void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
-                    hipStream_t st)
+                    const double *terrain, hipStream_t st)
 {
     if (p.ms0) {  // single shooting: every knot simulated (k_rollout_ss)
-        LAUNCH_EL(k_rollout_ss, dim3((p.B + 3) / 4), dim3(64), st, p, d, eps, init, tix);
+        LAUNCH_EL_TR(k_rollout_ss, dim3((p.B + 3) / 4), dim3(64), st, p, d, eps, init, tix);
         return;
     }
     // slot waves, then the phase-boundary waves (k_rollout, rollout_boundary)
@@ -1795,28 +1816,28 @@ void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int in
     const bool wide = p.S >= RW;  // (rollout_block)
     if (fused_decide(p)) {
         if (p.elem_layout) {
-            if (wide) hipLaunchKernelGGL((k_rollout<true, true, true>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
-            else hipLaunchKernelGGL((k_rollout<true, true, false>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
+            if (wide) LAUNCH_TR((k_rollout<true, true, true>), g, dim3(64), st, p, d, eps, init, tix, last, budget);
+            else LAUNCH_TR((k_rollout<true, true, false>), g, dim3(64), st, p, d, eps, init, tix, last, budget);
         } else {
-            if (wide) hipLaunchKernelGGL((k_rollout<false, true, true>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
-            else hipLaunchKernelGGL((k_rollout<false, true, false>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
+            if (wide) LAUNCH_TR((k_rollout<false, true, true>), g, dim3(64), st, p, d, eps, init, tix, last, budget);
+            else LAUNCH_TR((k_rollout<false, true, false>), g, dim3(64), st, p, d, eps, init, tix, last, budget);
         }
         return;
     }
     if (p.elem_layout) {
-        if (wide) hipLaunchKernelGGL((k_rollout<true, false, true>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
-        else hipLaunchKernelGGL((k_rollout<true, false, false>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
+        if (wide) LAUNCH_TR((k_rollout<true, false, true>), g, dim3(64), st, p, d, eps, init, tix, last, budget);
+        else LAUNCH_TR((k_rollout<true, false, false>), g, dim3(64), st, p, d, eps, init, tix, last, budget);
     } else {
-        if (wide) hipLaunchKernelGGL((k_rollout<false, false, true>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
-        else hipLaunchKernelGGL((k_rollout<false, false, false>), g, dim3(64), 0, st, p, d, eps, init, tix, last, budget);
+        if (wide) LAUNCH_TR((k_rollout<false, false, true>), g, dim3(64), st, p, d, eps, init, tix, last, budget);
+        else LAUNCH_TR((k_rollout<false, false, false>), g, dim3(64), st, p, d, eps, init, tix, last, budget);
     }
-    if (p.has_tail) LAUNCH_EL(k_rollout_tail, dim3((p.B + 63) / 64), dim3(64), st, p, d, eps, init, tix);
+    if (p.has_tail) LAUNCH_EL_TR(k_rollout_tail, dim3((p.B + 63) / 64), dim3(64), st, p, d, eps, init, tix);
 }
 void launch_decide(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
-                   hipStream_t st)
+                   const double *terrain, hipStream_t st)
 {
     if (fused_decide(p)) return;  // decided by the rollout launch
-    LAUNCH_EL(k_decide, dim3((p.B + 3) / 4), dim3(64), st, p, d, eps, last, init, tix, budget);
+    LAUNCH_EL_TR(k_decide, dim3((p.B + 3) / 4), dim3(64), st, p, d, eps, last, init, tix, budget);
 }
 void launch_normalize(const Params &p, const Bufs &d, hipStream_t st)
 {
@@ -1830,15 +1851,15 @@ void launch_normalize(const Params &p, const Bufs &d, hipStream_t st)
 // follows starts empty (its only reader before then is the previous iteration's
 // k_riccati_select), no element has been seen searching after any trial yet (ls_live), and
 // k_count's activity counts start from zero (the graph-replayed iteration has no memset launches).
-template <bool EL>
-__global__ __launch_bounds__(128, 4) void k_terminal(Params p, Bufs d)
+template <bool EL, typename... TR>
+__global__ __launch_bounds__(128, 4) void k_terminal(Params p, Bufs d, TR... tr)
 {
     __shared__ TermLds S[2 * TERM_TPW];
     const int w = threadIdx.x >> 6;
-    terminal_wave<EL>(p, d, S + w * TERM_TPW, (long)blockIdx.x * 2 + w, threadIdx.x & 63);
+    terminal_wave<EL>(p, d, terrain_of(tr...), S + w * TERM_TPW, (long)blockIdx.x * 2 + w, threadIdx.x & 63);
 }
 
-void launch_lq(const Params &p, const Bufs &d, hipStream_t st)
+void launch_lq(const Params &p, const Bufs &d, const double *terrain, hipStream_t st)
 {
     // the terminal waves: a launch of their own (five waves per SIMD), or, for a small batch whose
     // knot and terminal blocks all fit the chip at once (C1: one robot), the blocks after k_lq's
@@ -1848,15 +1869,14 @@ void launch_lq(const Params &p, const Bufs &d, hipStream_t st)
     const bool by_knot = !p.lq_slots && !p.fp32;  // k_lq's grid: control knots or state slots
     if (!merged) {
         const unsigned nt2 = blocks_for((long)p.B * p.P, 2 * TERM_TPW);
-        if (p.elem_layout) hipLaunchKernelGGL((k_terminal<true>), dim3(nt2), dim3(128), 0, st, p, d);
-        else hipLaunchKernelGGL((k_terminal<false>), dim3(nt2), dim3(128), 0, st, p, d);
+        LAUNCH_EL_TR(k_terminal, dim3(nt2), dim3(128), st, p, d);
     }
     const dim3 g(blocks_for((long)p.B * (by_knot ? p.Kc : p.S), 256) + (merged ? nterm : 0));
     if (p.fp32) {
 #define HSDDP_LQ(f, e)                                                          \
     do {                                                                        \
-        if (p.lq_slots) hipLaunchKernelGGL((k_lq<f, e, true>), g, dim3(256), 0, st, p, d); \
-        else hipLaunchKernelGGL((k_lq<f, e, false>), g, dim3(256), 0, st, p, d);           \
+        if (p.lq_slots) LAUNCH_TR((k_lq<f, e, true>), g, dim3(256), st, p, d);  \
+        else LAUNCH_TR((k_lq<f, e, false>), g, dim3(256), st, p, d);            \
     } while (0)
         if (p.elem_layout) HSDDP_LQ(true, true);
         else HSDDP_LQ(true, false);
@@ -1887,9 +1907,9 @@ void launch_outer_begin(const Params &p, const Bufs &d, const int *budget, hipSt
 {
     hipLaunchKernelGGL(k_outer_begin, dim3(blocks_for(p.B, 256)), dim3(256), 0, st, p, d, budget);
 }
-void launch_reb_update(const Params &p, const Bufs &d, hipStream_t st)
+void launch_reb_update(const Params &p, const Bufs &d, const double *terrain, hipStream_t st)
 {
-    LAUNCH_EL(k_reb_update, dim3(blocks_for((long)p.B * p.Kc, 256)), dim3(256), st, p, d);
+    LAUNCH_EL_TR(k_reb_update, dim3(blocks_for((long)p.B * p.Kc, 256)), dim3(256), st, p, d);
 }
 void launch_outer_end(const Params &p, const Bufs &d, const int *budget, hipStream_t st)
 {

@@ -271,6 +271,32 @@ void shifted_layouts(const ShiftPlan &plan, std::vector<Layout> &lays, std::vect
     }
 }
 
+// ---- terrain ---------------------------------------------------------------------------------------
+void put_terrain_rows(const double *rows, int n, int P, const double *fill, double *out)
+{
+    for (int i = 0; i < P; ++i) {
+        const double *src = rows && i < n ? rows + 2 * i : fill;
+        out[2 * i] = src[0];
+        out[2 * i + 1] = src[1];
+    }
+}
+
+void shift_terrain(const HorizonView &v, const ShiftPlan &plan, int P, std::vector<double> &out)
+{
+    out.resize((size_t)v.B * P * 2);
+    for (int b = 0; b < v.B; ++b) {
+        const std::vector<ShiftPhase> &ph = plan.phs[plan.map_id[b]];
+        double *row = &out[(size_t)b * P * 2];
+        put_terrain_rows(nullptr, 0, P, v.fill, row);
+        for (int i = 0; i < (int)ph.size() && i < P; ++i) {
+            // (i = 0 without a source: an element whose rows the caller writes; they stay at fill)
+            const double *src = ph[i].src >= 0 ? &v.terrain[((size_t)b * v.P + ph[i].src) * 2] : i > 0 ? row + 2 * (i - 1) : v.fill;
+            row[2 * i] = src[0];
+            row[2 * i + 1] = src[1];
+        }
+    }
+}
+
 // ---- references ------------------------------------------------------------------------------------
 std::vector<float> clock_starts(const Layout &L, float dt_sim)
 {
@@ -517,6 +543,8 @@ void export_element(const HorizonView &v, int b, ElementImport &out)
     if (v.durations) std::copy_n(&v.durations[(size_t)b * v.P * 4], L.P * 4, out.durations);
     out.win_start = v.win_start ? v.win_start[v.Bref == 1 ? 0 : b] : 0;
     out.clock = v.t_el ? v.t_el[b] : v.t_cur;
+    out.has_terrain = v.terrain ? 1 : 0;
+    if (v.terrain) std::copy_n(&v.terrain[(size_t)b * v.P * 2], L.P * 2, out.terrain);
 }
 
 int plan_import_batch(const HorizonView &v, const std::vector<int> &list, const ElementImport *in, RestartBatch &r,

@@ -123,6 +123,8 @@ struct HorizonView {
     float dt_sim;
     float t_cur;            // QuadReference::t_cur of the batch, or
     const float *t_el;      // [B] each element's own (null: t_cur)
+    const double *terrain;  // [B][P][2] (mu, ground) per phase (hsddp_set_terrain), or null: off
+    double fill[2];         // the handle's cparams pair: the row of a phase without one of its own
 
     const Layout &layout(int b) const { return lays ? lays[b] : *shared; }
     const int *reach_of(int b) const { return lays ? reach + (size_t)b * MAXP : reach; }
@@ -155,6 +157,16 @@ struct ShiftMaps {
 int flatten_shift(const ShiftPlan &plan, int Kc, size_t S_cap, ShiftMaps &m, std::string &why);
 // the elements' layouts and reach flags [B][MAXP] after a plan of several maps
 void shifted_layouts(const ShiftPlan &plan, std::vector<Layout> &lays, std::vector<int> &reach);
+
+// ---- terrain ---------------------------------------------------------------------------------------
+// The per-phase (mu, ground) rows move with the phases as the contact durations do.  The view's
+// rows after a shift plan, [B][P][2] at the new stride P: an old phase keeps its row, a phase the
+// steps started takes the row of the phase before it (the element's previous last phase); the rows
+// past an element's phases, and an element whose first phase is new (its rows are a restart's or an
+// arriving element's to write), hold the view's fill.  (Reads the view's terrain and fill only.)
+void shift_terrain(const HorizonView &v, const ShiftPlan &plan, int P, std::vector<double> &out);
+// one element's rows at stride P: its own n rows (null: fill), fill past them
+void put_terrain_rows(const double *rows, int n, int P, const double *fill, double *out);
 
 // ---- references ------------------------------------------------------------------------------------
 // the phases' start times on the float clock of HKDProblem::initialization (t += dt_sim per knot)
@@ -260,6 +272,8 @@ struct ElementImport {
     double durations[MAXP * 4];
     int win_start;
     float clock;
+    int has_terrain;              // the source's terrain was on: terrain holds the element's rows
+    double terrain[MAXP * 2];     // (mu, ground) per phase
 };
 // element b of the view
 void export_element(const HorizonView &v, int b, ElementImport &out);

@@ -14,6 +14,7 @@ struct SimArgs {
     hsddp_sim_sample *summary;  // [B][M], or null
     double *X, *U;              // [B][M][n_steps][24] zeroed by the caller, or null
 };
-void launch_simulate_policy(const Params &p, const Bufs &d, const SimArgs &a, hipStream_t st);
+// terrain: the per-phase (mu, ground) pairs min_grf / max_td are taken against, or null (hsddp_internal.h)
+void launch_simulate_policy(const Params &p, const Bufs &d, const SimArgs &a, const double *terrain, hipStream_t st);
 
 }  // namespace hsddp

@@ -34,9 +34,11 @@ struct KnotAt {
     int i, k, s;
 };
 
-template <bool EL>
-__global__ __launch_bounds__(64) void k_simulate_policy(Params p, Bufs d, SimArgs a)
+// tr: the terrain table, or nothing (TerrT, hsddp_device.h)
+template <bool EL, typename... TR>
+__global__ __launch_bounds__(64) void k_simulate_policy(Params p, Bufs d, SimArgs a, TR... tr)
 {
+    const auto terr = terrain_of(tr...);
     __shared__ double sh[PK];
     const int chunks = (a.M + 63) / 64;
     const int b = blockIdx.x / chunks, lane = threadIdx.x, m = (blockIdx.x % chunks) * 64 + lane;
@@ -140,11 +142,12 @@ __global__ __launch_bounds__(64) void k_simulate_policy(Params p, Bufs d, SimArg
                 const double *xr = sh + PK_XR, *ur = sh + PK_UR, *pf = sh + PK_PF;
                 const double lt = cost_tracking(p, c, x, xr), lu = cost_control(p, u, ur), lf = cost_foot(p, c, x, xr, pf);
                 cost += cost_combine(p, c, lt, lu, lf, 0.0);  // (no ReB term)
+                const double mu = terr.mu(p, b, i);
 #pragma unroll
                 for (int l = 0; l < 4; ++l) {
                     if (!c[l]) continue;
 #pragma unroll
-                    for (int r = 0; r < 5; ++r) min_grf = fmin(min_grf, grf_value(p.mu, r, u + 3 * l));
+                    for (int r = 0; r < 5; ++r) min_grf = fmin(min_grf, grf_value(mu, r, u + 3 * l));
                 }
                 steps = kc + 1;
 #pragma unroll
@@ -154,10 +157,11 @@ __global__ __launch_bounds__(64) void k_simulate_policy(Params p, Bufs d, SimArg
                     const double *xe = ref_ptr(p, d.ref_x, b, se, NX), *pe = ref_ptr(p, d.ref_foot, b, se, 12);
                     const int none[MTD] = {0, 0, 0, 0};  // (no AL term)
                     double tv;
+                    const double ground = terr.ground(p, b, i);
                     cost += terminal_cost_h(p, c, x, xe, pe, none, nullptr, nullptr, nullptr, tv);
 #pragma unroll
                     for (int l = 0; l < 4; ++l)
-                        if (touchdown(c, cn, l)) max_td = fmax(max_td, fabs(hkd_foot_height_grad(l, x, nullptr) - p.ground));
+                        if (touchdown(c, cn, l)) max_td = fmax(max_td, fabs(hkd_foot_height_grad(l, x, nullptr) - ground));
                     if (i + 1 < P) {
                         hkd_resetmap(x, c, cn, xs);
 #pragma unroll
@@ -177,9 +181,14 @@ __global__ __launch_bounds__(64) void k_simulate_policy(Params p, Bufs d, SimArg
     }
 }
 
-void launch_simulate_policy(const Params &p, const Bufs &d, const SimArgs &a, hipStream_t st)
+void launch_simulate_policy(const Params &p, const Bufs &d, const SimArgs &a, const double *terrain, hipStream_t st)
 {
     const unsigned grid = (unsigned)p.B * (unsigned)((a.M + 63) / 64);
+    if (terrain) {
+        if (p.elem_layout) hipLaunchKernelGGL(k_simulate_policy<true>, dim3(grid), dim3(64), 0, st, p, d, a, terrain);
+        else hipLaunchKernelGGL(k_simulate_policy<false>, dim3(grid), dim3(64), 0, st, p, d, a, terrain);
+        return;
+    }
     if (p.elem_layout) hipLaunchKernelGGL(k_simulate_policy<true>, dim3(grid), dim3(64), 0, st, p, d, a);
     else hipLaunchKernelGGL(k_simulate_policy<false>, dim3(grid), dim3(64), 0, st, p, d, a);
 }

@@ -88,7 +88,7 @@ static int solve_check(hsddp_handle h)
     if (h->need_inputs) return fail(HSDDP_ERR_ARG, "the layout changed (hsddp_shift): call hsddp_update_problem first");
     HIPCHK(hipSetDevice(h->desc.device));
     h->sim_fresh = false;  // the policy changes: a simulation held is of the old one
-    return HSDDP_OK;
+    return sync_terrain(h);
 }
 
 static std::vector<double> ls_steps(double alpha)
@@ -113,8 +113,8 @@ static void begin_launches(hsddp_handle h)
     if (h->p.trace) hipMemsetAsync(h->d.dbg, 0, (size_t)h->p.B * 16 * sizeof(unsigned long long), h->stream);
     sync_ref_columns(h);
     launch_reset_elements(h->p, h->d, h->stream);
-    launch_rollout(h->p, h->d, 0.0, 0, 1, -1, budget_of(h), h->stream);
-    launch_decide(h->p, h->d, 0.0, 0, 1, -1, budget_of(h), h->stream);
+    launch_rollout(h->p, h->d, 0.0, 0, 1, -1, budget_of(h), terrain_of(h), h->stream);
+    launch_decide(h->p, h->d, 0.0, 0, 1, -1, budget_of(h), terrain_of(h), h->stream);
     h->slots_fresh = true;
 }
 
@@ -129,7 +129,7 @@ static void iteration_launches(hsddp_handle h, const std::vector<double> &trials
         // line-search trial, quirk A2) unless the cost parameters changed since (slots_fresh)
         Params pl = p;
         pl.lq_slots = h->slots_fresh ? 0 : 1;
-        launch_lq(pl, d, st);
+        launch_lq(pl, d, terrain_of(h), st);
     }
     tm.end(0, e0);
     tm.begin(1, e0);
@@ -144,8 +144,8 @@ static void iteration_launches(hsddp_handle h, const std::vector<double> &trials
     }
     tm.begin(2, e0);
     for (size_t t = 0; t < trials.size(); ++t) {
-        launch_rollout(p, d, trials[t], t + 1 == trials.size(), 0, (int)t, budget_of(h), st);
-        launch_decide(p, d, trials[t], t + 1 == trials.size(), 0, (int)t, budget_of(h), st);
+        launch_rollout(p, d, trials[t], t + 1 == trials.size(), 0, (int)t, budget_of(h), terrain_of(h), st);
+        launch_decide(p, d, trials[t], t + 1 == trials.size(), 0, (int)t, budget_of(h), terrain_of(h), st);
     }
     tm.end(2, e0);
     h->slots_fresh = true;
@@ -171,7 +171,8 @@ static int graph_launch(hsddp_handle h, const std::vector<double> &trials, int p
     hsddp_handle_t::IterGraph *hit = nullptr;
     for (auto &c : h->iter_graph)
         if (c.exec && c.par == par && !std::memcmp(&c.p, &pl, sizeof(Params)) &&
-            !std::memcmp(&c.d, &h->d, sizeof(Bufs)) && c.alpha == h->opt.alpha && c.budget == budget_of(h))
+            !std::memcmp(&c.d, &h->d, sizeof(Bufs)) && c.alpha == h->opt.alpha && c.budget == budget_of(h) &&
+            c.terrain == terrain_of(h))
             hit = &c;
     if (!hit) {
         auto &g = h->iter_graph[h->iter_graph_next];
@@ -202,6 +203,7 @@ static int graph_launch(hsddp_handle h, const std::vector<double> &trials, int p
         std::memcpy(&g.d, &h->d, sizeof(Bufs));
         g.alpha = h->opt.alpha;
         g.budget = budget_of(h);
+        g.terrain = terrain_of(h);  // (null: terrain off — other instantiations, other arguments)
         g.par = par;
         hit = &g;
     }
@@ -228,7 +230,7 @@ static void outer_end_launches(hsddp_handle h, Timer &tm)
         h->slots_fresh = false;
         h->reb_at_init = false;
     }
-    if (h->opt.ReB_active) launch_reb_update(h->p, h->d, h->stream);
+    if (h->opt.ReB_active) launch_reb_update(h->p, h->d, terrain_of(h), h->stream);
     launch_outer_end(h->p, h->d, budget_of(h), h->stream);
     tm.end(3, e0);
 }

@@ -161,6 +161,27 @@ public:
         pending_states = states;
     }
 
+    // Per-robot terrain (hsddp_set_terrain): the robot's friction coefficient and touchdown ground
+    // height on every phase of its horizon, from the next solve on.  The rows move with the robot's
+    // phases (a phase entering the horizon takes the row of the one before it), so one call lasts
+    // until the next; restart() and initialize() return a robot to the settings' pair.  Within a
+    // tick the order is advance -> (restart) -> set_terrain -> x0 -> solve: call between ticks.
+    void set_terrain(int robot, double mu, double ground)
+    {
+        if (robot < 0 || robot >= B) throw std::runtime_error("set_terrain: no such robot");
+        wait();
+        std::lock_guard<std::mutex> lk(mpc_mutex);
+        int Ps = 0;
+        chk(hsddp_get_strides(h, &Ps, nullptr));
+        std::vector<double> m((size_t)B * Ps), g((size_t)B * Ps);
+        chk(hsddp_get_terrain(h, m.data(), g.data()));
+        for (int i = 0; i < Ps; ++i) {
+            m[(size_t)robot * Ps + i] = mu;
+            g[(size_t)robot * Ps + i] = ground;
+        }
+        chk(hsddp_set_terrain(h, m.data(), g.data()));
+    }
+
     // HKDMPCSolver::mpcdata_lcm_handler (HKDMPC.cpp:166-200): msgs[B]
     void mpcdata_lcm_handler(const std::vector<hkd_data_lcmt> &msgs)
     {

@@ -1355,6 +1355,10 @@ public:
         std::vector<double> al_sigma, al_lambda, reb_delta, reb_eps;
         std::vector<int> contacts;
         std::vector<double> ref_x, ref_u, ref_foot, Xbar, Ubar, K;
+        // per-phase terrain (hsddp_set_terrain) [P]: each phase's GRF friction coefficient and its
+        // touchdown constraints' ground height; empty when the phases agree (desc.cparams carries the
+        // pair, as it does for a handle without terrain)
+        std::vector<double> mu, ground;
     };
     Problem describe();
 
@@ -1715,6 +1719,9 @@ typename MultiPhaseDDP<T>::Problem MultiPhaseDDP<T>::describe()
     pr.al_lambda.assign((size_t)P * HSDDP_MAX_TD * 4, cp0.td_lambda);
     hsddp_facade::TdSpec td0;
     bool td_seen = false;
+    // (mu, ground) of every phase that has a GRF / a touchdown constraint: per-phase terrain
+    std::vector<double> ph_mu(P), ph_ground(P);
+    std::vector<char> has_mu(P, 0), has_ground(P, 0);
     for (int i = 0; i < P; ++i) {
         int slot = 0;
         for (auto &c : ph[i]->tconstraints) {
@@ -1728,10 +1735,14 @@ typename MultiPhaseDDP<T>::Problem MultiPhaseDDP<T>::describe()
             if (!mask) continue;  // no rows: no AL terms
             if (slot == HSDDP_MAX_TD)
                 refuse(i, "more than " + std::to_string(HSDDP_MAX_TD) + " touchdown constraints on one phase");
-            if (td_seen && (s.sigma_max != td0.sigma_max || s.ground != td0.ground))
-                refuse(i, "touchdown sigma_max / ground height differ from another constraint's (one set per handle)");
+            if (td_seen && s.sigma_max != td0.sigma_max)
+                refuse(i, "touchdown sigma_max differs from another constraint's (one per handle)");
+            if (has_ground[i] && s.ground != ph_ground[i])
+                refuse(i, "touchdown ground height differs from another constraint's of the same phase (one per phase)");
             if (!td_seen) td0 = s;
             td_seen = true;
+            ph_ground[i] = s.ground;
+            has_ground[i] = 1;
             const bool own = c->params.size() == (size_t)rows;  // initialize_params ran (else the defaults)
             if (!own && !c->params.empty()) refuse(i, "touchdown constraint parameters do not match its rows");
             pr.td_legs[(size_t)i * HSDDP_MAX_TD + slot] = mask;
@@ -1777,16 +1788,39 @@ typename MultiPhaseDDP<T>::Problem MultiPhaseDDP<T>::describe()
             for (int l = 0; l < 4; ++l)
                 if (s.contact[l] != pr.contacts[4 * i + l]) refuse(i, "GRF constraint contact differs from the phase's");
             ++n_grf;
-            if (grf_seen && (s.mu != g0.mu || s.delta_min != g0.delta_min))
-                refuse(i, "GRF friction coefficient / ReB delta_min differ from another phase's (one set per handle)");
+            if (grf_seen && s.delta_min != g0.delta_min)
+                refuse(i, "GRF ReB delta_min differs from another phase's (one per handle)");
             if (!grf_seen) g0 = s;
             grf_seen = true;
+            ph_mu[i] = s.mu;
+            has_mu[i] = 1;
         }
         if (stance > 0 && n_grf != 1) refuse(i, "a phase with stance legs needs exactly one GRF constraint");
     }
     if (grf_seen) {
         desc.cparams.mu_fric = g0.mu;
         desc.cparams.grf_delta = g0.delta; desc.cparams.grf_delta_min = g0.delta_min; desc.cparams.grf_eps = g0.eps;
+    }
+    // Phases that differ in mu or ground go to the handle as per-phase terrain.  The handle-wide pair
+    // is then the library's default (read by no phase that has a constraint), so the handle's key
+    // stays the same from tick to tick while the phases move through the horizon.  Phases that agree
+    // keep their pair in cparams and launch the kernels without a table, as before terrain existed;
+    // a horizon that passes from differing to agreeing phases (the differing one leaves) therefore
+    // changes the descriptor, and solve() then makes a new handle once — an allocation, not a
+    // different result: every solve uploads all the state the handle holds.
+    bool uniform = true;
+    for (int i = 0; i < P; ++i)
+        uniform = uniform && (!has_mu[i] || ph_mu[i] == desc.cparams.mu_fric) &&
+                  (!has_ground[i] || ph_ground[i] == desc.cparams.ground_height);
+    if (!uniform) {
+        desc.cparams.mu_fric = cp0.mu_fric;
+        desc.cparams.ground_height = cp0.ground_height;
+        pr.mu.assign(P, cp0.mu_fric);
+        pr.ground.assign(P, cp0.ground_height);
+        for (int i = 0; i < P; ++i) {
+            if (has_mu[i]) pr.mu[i] = ph_mu[i];
+            if (has_ground[i]) pr.ground[i] = ph_ground[i];
+        }
     }
     // costs: one tracking and one foot-placement term per phase
     std::vector<hsddp_facade::CostSpec> track(P), foot(P);
@@ -1940,6 +1974,9 @@ void MultiPhaseDDP<T>::solve(HSDDP_OPTION option)
     check(hsddp_upload_warm_start(handle, pr.Xbar.data(), pr.Ubar.data(), pr.K.data()));
     check(hsddp_upload_constraint_params(handle, pr.reb_delta.data(), pr.reb_eps.data(), pr.td_legs.data(),
                                          pr.al_sigma.data(), pr.al_lambda.data()));
+    // every tick: the reference's update creates new constraint objects (hsddp_set_layout above
+    // turned the last tick's terrain off)
+    if (!pr.mu.empty()) check(hsddp_set_terrain(handle, pr.mu.data(), pr.ground.data()));
     hsddp_stats st;
     check(hsddp_solve(handle, &st));
     // the constraint objects keep the parameters the solve's AL / ReB updates left (the next MPC

@@ -302,6 +302,34 @@ class Solver:
             arrs.append(a)
         check(lib().hsddp_upload_constraint_params(self._h, *(None if a is None else a.ctypes.data for a in arrs)))
 
+    def set_terrain(self, mu=None, ground=None) -> None:
+        """Per-phase terrain (hsddp_set_terrain): mu, ground [B][P] (P = self.P, the phase stride), the
+        friction coefficient of element b's phase i and the ground height of its touchdown
+        constraints.  None leaves that quantity at the handle's cparams value everywhere; both None
+        turn terrain off.  A scalar or a [B] array is spread over the phases.  The rows move with the
+        phases through shift / advance (an appended phase takes the row of the one before it), a
+        restart gives the restarted elements cparams rows.  Tick order: advance -> (restart) ->
+        set_terrain -> x0 -> solve."""
+        B, P = self.B, self.P
+        arrs = []
+        for name, a in (("mu", mu), ("ground", ground)):
+            if a is not None:
+                a = np.asarray(a, dtype=np.float64)
+                if a.ndim <= 1:
+                    a = a.reshape(-1, 1)
+                if a.shape not in ((1, 1), (B, 1), (B, P)):
+                    raise HSDDPError(f"{name}: shape {a.shape}, expected ({B}, {P}), ({B},) or a scalar")
+                a = np.ascontiguousarray(np.broadcast_to(a, (B, P)))
+            arrs.append(a)
+        check(lib().hsddp_set_terrain(self._h, *(None if a is None else dp(a) for a in arrs)))
+
+    def terrain(self) -> dict:
+        """{"mu", "ground"}: [B][P] each (hsddp_get_terrain); the cparams values for rows past an
+        element's phases, and everywhere while terrain is off."""
+        out = {"mu": np.empty((self.B, self.P)), "ground": np.empty((self.B, self.P))}
+        check(lib().hsddp_get_terrain(self._h, dp(out["mu"]), dp(out["ground"])))
+        return out
+
     def set_value_export(self, on: bool = True) -> None:
         """Store G[0], H[0] of every phase in each sweep (SinglePhase::get_value_approx)."""
         check(lib().hsddp_set_value_export(self._h, int(bool(on))))

@@ -127,6 +127,7 @@ EXPORTS = [
     "hsddp_hkd_state", "hsddp_update_problem_measured", "hsddp_extract_commands_measured",
     "hsddp_restart_elements", "hsddp_set_element_budgets", "hsddp_get_strides",
     "hsddp_copy_elements", "hsddp_element_record_bytes", "hsddp_export_elements", "hsddp_import_elements",
+    "hsddp_set_terrain", "hsddp_get_terrain",
 ]
 
 
@@ -227,6 +228,9 @@ def lib():
         L.hsddp_export_elements.restype = C.c_int
         L.hsddp_import_elements.argtypes = [V, C.c_int, IP, V]
         L.hsddp_import_elements.restype = C.c_int
+    if hasattr(L, "hsddp_set_terrain"):  # (older A/B builds lack the per-phase terrain)
+        L.hsddp_set_terrain.argtypes = [V, DP, DP]
+        L.hsddp_get_terrain.argtypes = [V, DP, DP]
     _lib = L
     return L
 

@@ -236,6 +236,36 @@ int hsddp_download_constraint_params(hsddp_handle h, double *reb_delta, double *
  * each touchdown constraint's legs (0 outside its mask).  Valid after hsddp_solve / solve_end,
  * before the next hsddp_shift.  Either pointer may be NULL. */
 int hsddp_download_constraint_values(hsddp_handle h, double *grf_g, double *td_h);
+/* Per-phase terrain: each element's friction coefficient and touchdown ground height, phase by
+ * phase, where desc->cparams gives one pair for the handle (the reference's
+ * GRFConstraint::set_friction_coefficient, one object per phase, and
+ * TouchDownConstraint::update_ground_height, one per touchdown; HKDConstraints.h:24,46).
+ * mu, ground [B][P] with P of hsddp_get_strides: mu[b][i] the friction coefficient of the GRF
+ * pyramid at every knot of element b's phase i, ground[b][i] the ground height of every touchdown
+ * constraint of that phase (its HSDDP_MAX_TD slots share it).  A NULL array leaves that quantity
+ * at the cparams value everywhere; both NULL turn terrain off, and the handle is what it was
+ * before the first call.  Rows past an element's own phases are not read.
+ * HSDDP_ERR_ARG (the handle unchanged): no problem uploaded, a non-finite value or mu <= 0 in a
+ * row that is read.
+ * Terrain is an input like the contact rows, not solver state: the call leaves the warm start,
+ * the constraint parameters and the stored constraint values alone (as the reference's setters
+ * leave data[].g / h until the next rollout).  It moves with the phases on every path, as the
+ * contact durations do: hsddp_shift / hsddp_shift_elements / hsddp_advance drop the row of a
+ * removed first phase and give an appended phase the row of the element's previous last phase, so
+ * an element set once keeps its values through every tick; hsddp_restart_elements gives the
+ * restarted elements cparams rows; hsddp_copy_elements / hsddp_export_elements /
+ * hsddp_import_elements carry an element's rows with it (a destination without terrain that
+ * receives an element with terrain turns it on, cparams rows elsewhere).
+ * hsddp_upload_problem, hsddp_upload_warm_start, hsddp_update_problem* and hsddp_set_options keep
+ * it; hsddp_set_layout and hsddp_set_element_layouts turn it off (the phases it described are
+ * gone).  The call is allowed while inputs are pending after hsddp_advance(.., x0 = NULL, ..) or
+ * hsddp_restart_elements, with the arrays at the new strides: that is where a caller sets the
+ * terrain of a phase that has just entered the horizon.  Tick order: advance -> (restart) ->
+ * set_terrain -> x0 -> solve. */
+int hsddp_set_terrain(hsddp_handle h, const double *mu, const double *ground);
+/* The terrain rows [B][P] (either pointer may be NULL): the cparams values for rows past an
+ * element's phases, and for every row while terrain is off. */
+int hsddp_get_terrain(hsddp_handle h, double *mu, double *ground);
 
 /* MultiPhaseDDP::solve (MultiPhaseDDP.cpp:232-428) for every element.  With early exits on, each
  * inner iteration is replayed from a cached hipGraph and stats carries ms_total but no per-phase

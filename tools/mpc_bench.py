@@ -68,9 +68,12 @@ def main():
                     help="x0 of every tick formed on the device from the same records (update_problem_measured)")
     ap.add_argument("--restart-frac", type=float, default=None,
                     help="restart this fraction of the robots every tick (per-robot reference windows; 0: an empty mask)")
+    ap.add_argument("--terrain", action="store_true",
+                    help="per-phase terrain (set_terrain): a random friction coefficient in [0.3, 0.9] per robot and a "
+                         "ground height within +-0.03 per phase, the whole table set again every tick after the advance")
     args = ap.parse_args()
-    if args.host_state + args.measured + args.closed_loop + (args.restart_frac is not None) > 1:
-        ap.error("--host-state, --measured, --closed-loop and --restart-frac are separate legs")
+    if args.host_state + args.measured + args.closed_loop + (args.restart_frac is not None) + args.terrain > 1:
+        ap.error("--host-state, --measured, --closed-loop, --restart-frac and --terrain are separate legs")
     B = args.batch
     tab, dt = hsddp.load_quad_reference(os.path.join(ROOT, "tests", "golden", "ref_trot.csv"))
     rng = np.random.default_rng(7)
@@ -84,7 +87,10 @@ def main():
     s.solve()
     s.set_options(hsddp.load_settings(max_AL_iter=2, max_DDP_iter=1))
     feet = np.tile(np.float32([.2, -.14, 0, .2, .14, 0, -.2, -.14, 0, -.2, .14, 0]), (B, 1))
-    t_adv, t_solve, t_cmd, t_plant, t_state, t_restart = [], [], [], [], [], []
+    t_adv, t_solve, t_cmd, t_plant, t_state, t_restart, t_terrain = [], [], [], [], [], [], []
+    if args.terrain:
+        rng_t = np.random.default_rng(13)
+        s.set_terrain(np.repeat(rng_t.uniform(0.3, 0.9, (B, 1)), s.P, axis=1), rng_t.uniform(-0.03, 0.03, (B, s.P)))
     n_restart = 0
     if restarts and args.restart_frac > 0:
         n_restart = min(B, max(1, int(round(args.restart_frac * B))))
@@ -130,6 +136,15 @@ def main():
             tr = time.perf_counter()
             s.restart_elements(mask, ws)
             t_restart.append(time.perf_counter() - tr)
+            s.update_problem(None, xt)
+        elif args.terrain:  # advance -> set_terrain -> x0 -> solve (the table goes up with the solve's first launch)
+            xt = x0 + rng.uniform(-.01, .01, x0.shape)
+            t0 = time.perf_counter()
+            flags += sum(s.advance(None, 1))
+            tt = time.perf_counter()
+            t = s.terrain()  # the rows the phases carried on; a phase that entered took the last one's
+            s.set_terrain(t["mu"], t["ground"])
+            t_terrain.append(time.perf_counter() - tt)
             s.update_problem(None, xt)
         else:
             xt = x0 + rng.uniform(-.01, .01, x0.shape)
@@ -188,6 +203,12 @@ def main():
             s.warm_start()
             t_up.append(time.perf_counter() - tu)
         out["ms_per_tick_median"]["reupload_all"] = med(t_up)
+    if args.terrain:
+        out["metric"] = "MPC tick with per-phase terrain (advance + set_terrain + x0 + solve + extract), HKD trot reference file"
+        out["ms_per_tick_median"]["advance"] = med(np.array(t_adv) - np.array(t_terrain))
+        out["ms_per_tick_median"]["terrain"] = med(t_terrain)
+        t = s.terrain()
+        out["terrain_mu_range"] = [float(t["mu"].min()), float(t["mu"].max())]
     if args.host_state or args.measured:
         out["metric"] = ("MPC tick from measured robot states, x0 formed on the %s, HKD trot reference file"
                          % ("device (update_problem_measured)" if args.measured else "host (foot-position primitive)"))
