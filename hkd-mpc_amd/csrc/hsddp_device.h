@@ -25,6 +25,14 @@ DEV void pin(T (&a)[N])
 // their registers) into an earlier one
 #define SFENCE() __builtin_amdgcn_sched_barrier(0)
 
+// LDS hand-over between the lanes of one wave (its LDS accesses complete in order)
+DEV void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // ---------------------------------------------------------------------------------------------
 // cost model helpers (HKDCost.h / HKDCost.cpp / SinglePhaseInterface.cpp:55-118)
 // Params read in place from the kernel-argument segment (scalar loads).  Every kernel takes Params

@@ -209,24 +209,55 @@ struct Bufs {
     double *value0;                        // [B][P][24 + 576]: G[0], H[0] per phase (store_value)
 };
 
-// kernel launchers (hsddp_kernels.hip)
+// Kernel launchers, grouped by the file that defines them.
+//
+// One DDP inner iteration of MultiPhaseDDP::solve (HSDDPSolver/source/MultiPhaseDDP.cpp:304-381)
+// for B trajectories is:
+//   k_lq        knot-parallel  cost at (X, U) + compact LQ model   SinglePhase::compute_cost/LQ_approximation
+//   k_terminal  (elem, phase)  Phix, Phixx (+AL), reset Jacobian   SinglePhase.cpp:286-295; HKDReset.h:78-136
+//                              one wave per TERM_TPW tasks: a launch of its own before k_lq, or — at most
+//                              256 terminal blocks — the last blocks of the k_lq launch (launch_lq)
+//   k_riccati   one wave/2 elems regularised Riccati sweep over all phases   (hsddp_sweep.hip)
+//                              MultiPhaseDDP.cpp:141-229; SinglePhase.cpp:298-367
+//   k_lin_rollout one wave/2 elems  MS linear rollout + merit                (hsddp_linear.hip)
+//                              MultiPhaseDDP.cpp:20-50, 309-318; SinglePhase.cpp:144-178
+//   k_rollout   knot-parallel  one line-search trial (all knots are shooting states)  SinglePhase.cpp:181-233
+//   k_decide    per element    merit acceptance (MultiPhaseDDP.cpp:113-133) + inner-loop exit tests;
+//                              Trajectory::update_nominal_vals (TrajectoryManagement.cpp:110-115)
+//                              is its flip of the element's nominal buffer (no copies)
+// plus the outer AL/ReB updates (ConstraintsBase.h:168-183, 349-365; MultiPhaseDDP.cpp:383-408).
+//
+// Every element carries its own control-flow state (ElemState): regularisation retries, line-search
+// acceptance, early exits and AL/ReB updates are per-element masks, never lockstep.
+//
+// A launcher picks its kernel's instantiation from the handle's runtime flags (layout mode, terrain,
+// precision, ...) through with_flags / with_flags_table (hsddp_dispatch.h).
+//
 // terrain: the per-phase (mu, ground) pairs [B][P] (hsddp_set_terrain; the terrain instantiations),
 // or null: Params::mu / ::ground for every phase, the instantiations and arguments without terrain.
 // Not in Bufs: the kernels that never read it (the sweep, the linear rollout, the shift, ...) keep
 // their argument segments
+
+// ---- hsddp_lq.hip: the LQ model (k_lq) and the terminal tasks (k_terminal) ----
+void launch_lq(const Params &p, const Bufs &d, const double *terrain, hipStream_t st);
+
+// ---- hsddp_sweep.hip, hsddp_linear.hip ----
+void launch_riccati(const Params &p, const Bufs &d, hipStream_t st);
+void launch_lin_rollout(const Params &p, const Bufs &d, hipStream_t st);
+
+// ---- hsddp_rollout.hip: the forward line search ----
 // tix: the trial's index in the inner iteration's line search (-1: the initial rollout)
 // (last: this trial is the search's last step size — used when the rollout launch also decides)
 void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
                     const double *terrain, hipStream_t st);
 void launch_decide(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
                    const double *terrain, hipStream_t st);
+
+// ---- hsddp_outer.hip: the outer loop's updates and the element-state housekeeping ----
 // nominal rows of every element into buffer 0 (Bufs::sel bit 0 cleared), for host transfers
 void launch_normalize(const Params &p, const Bufs &d, hipStream_t st);
 // every element's working rows back at its nominal ones (sel), its Defect rows zero
 void launch_reset_working(const Params &p, const Bufs &d, hipStream_t st);
-void launch_lq(const Params &p, const Bufs &d, const double *terrain, hipStream_t st);
-void launch_riccati(const Params &p, const Bufs &d, hipStream_t st);
-void launch_lin_rollout(const Params &p, const Bufs &d, hipStream_t st);
 void launch_outer_begin(const Params &p, const Bufs &d, const int *budget, hipStream_t st);
 void launch_reb_update(const Params &p, const Bufs &d, const double *terrain, hipStream_t st);
 void launch_outer_end(const Params &p, const Bufs &d, const int *budget, hipStream_t st);
@@ -245,7 +276,7 @@ void launch_stat_sums(const Params &p, const Bufs &d, hipStream_t st);
 // dst[c][n] = src[n] for c < copies
 void launch_broadcast(double *dst, const double *src, size_t n, size_t copies, hipStream_t st);
 
-// model primitives
+// ---- hsddp_model.hip: the facade's model and plugin primitives ----
 void launch_model_dynamics(const double *x, const double *u, const double *c, double dt, double *xn, int n,
                            hipStream_t st);
 void launch_model_partial(const double *x, const double *u, const double *c, double dt, double *A, double *B,

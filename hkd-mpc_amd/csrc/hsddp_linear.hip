@@ -6,6 +6,7 @@
 // change of quirk A3 (it replaces the sweep's dV).  Templates on `real` as the sweep
 // (hsddp_sweep.hip): double, or float in config C5's fp32 mode.
 #include "hsddp_wave.h"
+#include "hsddp_dispatch.h"
 
 namespace hsddp {
 
@@ -565,13 +566,10 @@ __global__ __launch_bounds__(64, 2) void k_lin_rollout(Params p, Bufs d)
 void launch_lin_rollout(const Params &p, const Bufs &d, hipStream_t st)
 {
     const dim3 g((unsigned)(p.elem_layout ? p.n_pairs : (p.B + 1) / 2));
-    if (p.fp32) {
-        if (p.elem_layout) hipLaunchKernelGGL((k_lin_rollout<float, true>), g, dim3(64), 0, st, p, d);
-        else hipLaunchKernelGGL((k_lin_rollout<float, false>), g, dim3(64), 0, st, p, d);
-    } else {
-        if (p.elem_layout) hipLaunchKernelGGL((k_lin_rollout<double, true>), g, dim3(64), 0, st, p, d);
-        else hipLaunchKernelGGL((k_lin_rollout<double, false>), g, dim3(64), 0, st, p, d);
-    }
+    with_flags([&](auto f32, auto el) {
+        using real = std::conditional_t<decltype(f32)::value, float, double>;
+        hipLaunchKernelGGL((k_lin_rollout<real, decltype(el)::value>), g, dim3(64), 0, st, p, d);
+    }, p.fp32, p.elem_layout);
 }
 
 }  // namespace hsddp

@@ -16,6 +16,7 @@
 #include <cstddef>
 #include "../../include/hsddp.h"
 #include "hsddp_device.h"
+#include "hsddp_dispatch.h"
 #include "hsddp_mpc.h"
 
 namespace hsddp {
@@ -370,8 +371,9 @@ void launch_build_refs(const Params &p, const Bufs &d, int Bref, const RefArgs &
 void launch_extract_commands(const Params &p, const Bufs &d, const CmdArgs &a, hsddp_mpc_command *out,
                              hipStream_t st)
 {
-    if (p.elem_layout) hipLaunchKernelGGL(k_extract_commands<true>, dim3(p.B), dim3(256), 0, st, p, d, a, out);
-    else hipLaunchKernelGGL(k_extract_commands<false>, dim3(p.B), dim3(256), 0, st, p, d, a, out);
+    with_flags([&](auto el) {
+        hipLaunchKernelGGL(k_extract_commands<decltype(el)::value>, dim3(p.B), dim3(256), 0, st, p, d, a, out);
+    }, p.elem_layout);
 }
 
 }  // namespace hsddp

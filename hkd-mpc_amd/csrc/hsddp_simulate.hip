@@ -8,6 +8,7 @@
 #include "hsddp_simulate.h"
 
 #include "hsddp_device.h"
+#include "hsddp_dispatch.h"
 
 namespace hsddp {
 
@@ -184,13 +185,9 @@ __global__ __launch_bounds__(64) void k_simulate_policy(Params p, Bufs d, SimArg
 void launch_simulate_policy(const Params &p, const Bufs &d, const SimArgs &a, const double *terrain, hipStream_t st)
 {
     const unsigned grid = (unsigned)p.B * (unsigned)((a.M + 63) / 64);
-    if (terrain) {
-        if (p.elem_layout) hipLaunchKernelGGL(k_simulate_policy<true>, dim3(grid), dim3(64), 0, st, p, d, a, terrain);
-        else hipLaunchKernelGGL(k_simulate_policy<false>, dim3(grid), dim3(64), 0, st, p, d, a, terrain);
-        return;
-    }
-    if (p.elem_layout) hipLaunchKernelGGL(k_simulate_policy<true>, dim3(grid), dim3(64), 0, st, p, d, a);
-    else hipLaunchKernelGGL(k_simulate_policy<false>, dim3(grid), dim3(64), 0, st, p, d, a);
+    with_flags_table([&](auto el, auto... tr) {
+        hipLaunchKernelGGL(k_simulate_policy<decltype(el)::value>, dim3(grid), dim3(64), 0, st, p, d, a, tr...);
+    }, terrain, p.elem_layout);
 }
 
 }  // namespace hsddp

@@ -46,6 +46,7 @@
 //
 // Templates on `real`: double (the reference's T = double) and float (config C5's fp32 mode).
 #include "hsddp_wave.h"
+#include "hsddp_dispatch.h"
 
 namespace hsddp {
 
@@ -1441,56 +1442,43 @@ static int sweep_wpb(const Params &p)
     return pairs > cus && pairs <= 4 * cus ? 2 : 1;  // at most one wave per SIMD (4 per CU)
 }
 
+// k_riccati for one precision and wave count per workgroup (axes that are not flags: fp32 has W = 1 only)
+template <typename real, int W>
+static void launch_sweep(const Params &p, const Bufs &d, dim3 gw, int masks, hipStream_t st)
+{
+    with_flags([&](auto el, auto dv) {
+        hipLaunchKernelGGL((k_riccati<real, decltype(el)::value, decltype(dv)::value, W>), gw, dim3(64 * W), 0, st, p, d, masks);
+    }, p.elem_layout, p.ms0);
+}
+// the parallel retries of the elements whose first sweep failed, then the first success of each
+template <typename real>
+static void launch_retry(const Params &p, const Bufs &d, int masks, hipStream_t st)
+{
+    const dim3 gr((unsigned)(p.retry_cap * (p.retry_m + (p.retry_m & 1)) / 2)), gs((unsigned)p.retry_cap);
+    with_flags([&](auto el, auto dv) {
+        hipLaunchKernelGGL((k_riccati_retry<real, decltype(el)::value, decltype(dv)::value>), gr, dim3(64), 0, st, p, d, masks);
+    }, p.elem_layout, p.ms0);
+    hipLaunchKernelGGL(k_riccati_select<real>, gs, dim3(64), 0, st, p, d);
+}
+
 void launch_riccati(const Params &p, const Bufs &d, hipStream_t st)
 {
     // (the retry list count is zeroed by the k_lq launch just before, in its first terminal task)
     const dim3 g1((unsigned)(p.elem_layout ? p.n_pairs : (p.B + 1) / 2));
     // instantiations: precision x layout mode x single shooting (DV)
-#define HSDDP_RIC(kern, grid, real)                                                                          \
-    do {                                                                                                     \
-        if (p.ms0) {                                                                                         \
-            if (p.elem_layout) hipLaunchKernelGGL((kern<real, true, true>), grid, dim3(64), 0, st, p, d, masks); \
-            else hipLaunchKernelGGL((kern<real, false, true>), grid, dim3(64), 0, st, p, d, masks);            \
-        } else {                                                                                             \
-            if (p.elem_layout) hipLaunchKernelGGL((kern<real, true, false>), grid, dim3(64), 0, st, p, d, masks); \
-            else hipLaunchKernelGGL((kern<real, false, false>), grid, dim3(64), 0, st, p, d, masks);           \
-        }                                                                                                    \
-    } while (0)
     const int wpb = sweep_wpb(p), masks = sweep_masks();
     const dim3 gw((unsigned)(((p.elem_layout ? p.n_pairs : (p.B + 1) / 2) + wpb - 1) / wpb));
-#define HSDDP_RIC_W(real, W)                                                                                   \
-    do {                                                                                                       \
-        if (p.ms0) {                                                                                           \
-            if (p.elem_layout) hipLaunchKernelGGL((k_riccati<real, true, true, W>), gw, dim3(64 * W), 0, st, p, d, masks);  \
-            else hipLaunchKernelGGL((k_riccati<real, false, true, W>), gw, dim3(64 * W), 0, st, p, d, masks);        \
-        } else {                                                                                               \
-            if (p.elem_layout) hipLaunchKernelGGL((k_riccati<real, true, false, W>), gw, dim3(64 * W), 0, st, p, d, masks); \
-            else hipLaunchKernelGGL((k_riccati<real, false, false, W>), gw, dim3(64 * W), 0, st, p, d, masks);       \
-        }                                                                                                      \
-    } while (0)
-    if (p.fp32) HSDDP_RIC_W(float, 1);
-    else if (sweep_split(p)) {
-        if (p.ms0) {
-            if (p.elem_layout) hipLaunchKernelGGL((k_riccati_cs<true, true>), g1, dim3(128), 0, st, p, d);
-            else hipLaunchKernelGGL((k_riccati_cs<false, true>), g1, dim3(128), 0, st, p, d);
-        } else {
-            if (p.elem_layout) hipLaunchKernelGGL((k_riccati_cs<true, false>), g1, dim3(128), 0, st, p, d);
-            else hipLaunchKernelGGL((k_riccati_cs<false, false>), g1, dim3(128), 0, st, p, d);
-        }
-    } else if (wpb == 2) HSDDP_RIC_W(double, 2);
-    else HSDDP_RIC_W(double, 1);
-#undef HSDDP_RIC_W
+    if (p.fp32) launch_sweep<float, 1>(p, d, gw, masks, st);
+    else if (sweep_split(p))
+        with_flags([&](auto el, auto dv) {
+            hipLaunchKernelGGL((k_riccati_cs<decltype(el)::value, decltype(dv)::value>), g1, dim3(128), 0, st, p, d);
+        }, p.elem_layout, p.ms0);
+    else if (wpb == 2) launch_sweep<double, 2>(p, d, gw, masks, st);
+    else launch_sweep<double, 1>(p, d, gw, masks, st);
     if (p.retry_cap > 0) {
-        const dim3 gr((unsigned)(p.retry_cap * (p.retry_m + (p.retry_m & 1)) / 2)), gs((unsigned)p.retry_cap);
-        if (p.fp32) {
-            HSDDP_RIC(k_riccati_retry, gr, float);
-            hipLaunchKernelGGL(k_riccati_select<float>, gs, dim3(64), 0, st, p, d);
-        } else {
-            HSDDP_RIC(k_riccati_retry, gr, double);
-            hipLaunchKernelGGL(k_riccati_select<double>, gs, dim3(64), 0, st, p, d);
-        }
+        if (p.fp32) launch_retry<float>(p, d, masks, st);
+        else launch_retry<double>(p, d, masks, st);
     }
-#undef HSDDP_RIC
 }
 
 }  // namespace hsddp

@@ -47,7 +47,7 @@ pytestmark = pytest.mark.gpu
 
 FIXED = dict(no_early_exit=1, max_AL_iter=1, max_DDP_iter=3)
 TROT, JUMP = ("trot", 4, 16), ("jump", 8, 8)
-TERM_TASKS_PER_BLOCK = 8   # 4 x TERM_TPW (hsddp_kernels.hip: launch_lq)
+TERM_TASKS_PER_BLOCK = 8   # 4 x TERM_TPW (hsddp_lq.hip: launch_lq)
 TERM_MERGED_BLOCKS = 256   # ... whose threshold is a block count, not the CU count
 
 

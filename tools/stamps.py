@@ -50,7 +50,7 @@ def main():
     for name, c in zip(LIN_STAGES, lc):
         print(f"{name:28s} {c / (3 * 200):10.0f} cycles/knot  {100 * c / max(lt, 1):5.1f} %")
     print(f"{'total':28s} {lt / (3 * 200):10.0f} cycles/knot")
-    # k_rollout slot waves (hsddp_kernels.hip RSTAMP): element 0's slots 12..15, element 1's 0..3
+    # k_rollout slot waves (hsddp_rollout.hip RSTAMP): element 0's slots 12..15, element 1's 0..3
     flat = out.reshape(-1)
     rc = flat[12:19].astype(np.float64)
     nw = max(float(flat[19]), 1.0)
