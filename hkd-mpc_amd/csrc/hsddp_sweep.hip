@@ -83,6 +83,22 @@ namespace sweep {
     } while (0)
 #endif
 
+// Wave priority by knot stage (DESIGN.md §3.1 "Wave priority").  With two sweep waves on a SIMD the
+// issue arbiter takes the older ready wave first at equal priority, so the younger wave's latency
+// chains (a few dependent instructions between LDS round trips) wait behind the older wave's dense
+// multiply-add stages: the older wave of each SIMD ran ahead (11.9 k against 15.4 k cycles per knot)
+// and the kernel lasted as long as the younger.  A knot therefore raises its wave's priority for its
+// chains and drops it for the dense stages (a chain costs the partner 4 cycles per instruction it
+// lets through), and the two waves take turns and end together: sweep -8 % at B = 4096.  Three
+// levels: the chain stages (coefficient reads; Qxx through the K broadcast), the mixed stage
+// (M columns, Z, Qux_c) and the dense stages (Gn / T / M rows; the value update, where the knot ends,
+// so everything outside the knot loop runs at 0).  s_setprio is scalar and ignores EXEC: PRIO() stands
+// only in wave-uniform straight-line code.  The one-wave sweep only: the column split's launches have
+// one wave per SIMD and nobody to arbitrate against, and there the five instructions per knot cost
+// 0.4 % of a batch-1 solve (measured), so knot<W >= 0> compiles them out.
+constexpr int PRIO_DENSE = 0, PRIO_MIXED = 1, PRIO_CHAIN = 2;
+#define PRIO(level) __builtin_amdgcn_s_setprio(level)
+
 // stage boundary: LDS accesses stay in their stage and the scheduler does not interleave stages
 // (which would keep both stages' operands live)
 #define SSYNC()                              \
@@ -495,6 +511,7 @@ DEV void knot(real dt, LdsT &S, const Lane &L, const Phase<real> &ph, const Item
     const real reg = it.reg;
     const int cmask = MASK >= 0 ? MASK : ph.cmask;  // (MASK >= 0: the selects on it fold)
     if constexpr (!CS) STAMP(0);
+    if constexpr (!CS) PRIO(PRIO_CHAIN);
     // this knot's images: a phase's first knot waits for them here (split: each wave for its own
     // requests, then both), every other knot's landed before the previous knot's output stores (end
     // of knot)
@@ -510,6 +527,7 @@ DEV void knot(real dt, LdsT &S, const Lane &L, const Phase<real> &ph, const Item
 #pragma unroll
     for (int l = 0; l < 4; ++l) { bv[l] = I.pc[l]; bq[l] = I.pc[4 + l]; }
     if constexpr (!CS) STAMP(1);
+    if constexpr (!CS) PRIO(PRIO_DENSE);
     // ---- Gn = G + H d (SinglePhase.cpp:320), T = H B_c, M = H A (row pp) ----------------------
     // T and Gn read H first; M = H + H S then accumulates over H's registers (H is not read again:
     // the knot ends by forming the new H) from copies of the 9 entries S's rows read
@@ -540,6 +558,7 @@ DEV void knot(real dt, LdsT &S, const Lane &L, const Phase<real> &ph, const Item
     }
     if constexpr (CS) CSYNC(); else SSYNC();
     if constexpr (!CS) STAMP(2);
+    if constexpr (!CS) PRIO(PRIO_MIXED);
     // ---- column pp of M (position 24: Gn); Z row, Qux_c column, Qu_c ---------------------------
     const int pc = pp < MS - 1 ? pp : MS - 1;
     real mc[NX];
@@ -559,6 +578,7 @@ DEV void knot(real dt, LdsT &S, const Lane &L, const Phase<real> &ph, const Item
     pin(m);
     pin(w2);
     if constexpr (!CS) STAMP(3);
+    if constexpr (!CS) PRIO(PRIO_CHAIN);  // (held through Qxx, the Quu_cc columns, the elimination and the K broadcast)
     // ---- Qxx = lxx + reg I + (Z + Z^T) / 2 (SinglePhase.cpp:323-352) ---------------------------
     if (pp <= NX) {  // Z rows (two zero columns: the column reads of positions > 24 see zeros)
 #pragma unroll
@@ -679,6 +699,7 @@ DEV void knot(real dt, LdsT &S, const Lane &L, const Phase<real> &ph, const Item
         if (st) dvs += v;
     }
     if constexpr (!CS) STAMP(7);
+    if constexpr (!CS) PRIO(PRIO_DENSE);  // (to the knot's end: the stores, the loop's exits and the per-phase code run at 0)
     // ---- H = Qxx - Qux_c^T Quu_cc^-1 Qux_c = Qxx + Qux_c^T K_c (SinglePhase.cpp:360): row pp,
     // K_c by DPP broadcast from the lanes that hold its columns
     if constexpr (CS) {
