@@ -413,7 +413,7 @@ HKD_FN void hkd_foot_jacobian(int l, const double *eul, const double *q, double 
 }
 
 // foot height h and dh/dx in state order (TouchDownConstraint, HKDConstraints.cpp:69-171)
-HKD_FN double hkd_foot_height_grad(int l, const double *x, double *hx)
+__host__ __device__ __forceinline__ double hkd_foot_height_grad(int l, const double *x, double *hx)
 {
     Rot R, Dy, Dp, Dr;
     const EulTrig tr = eul_trig(x);

@@ -234,6 +234,8 @@ extern "C" int hsddp_destroy(hsddp_handle h)
     if (h->host_counter) hipHostFree(h->host_counter);
     if (h->terrain_pin) hipHostFree(h->terrain_pin);
     if (h->terrain_up) hipEventDestroy(h->terrain_up);
+    if (h->weights_pin) hipHostFree(h->weights_pin);
+    if (h->weights_up) hipEventDestroy(h->weights_up);
     if (h->copy_stream) hipStreamSynchronize(h->copy_stream);
     for (int q = 0; q < 2; ++q) {
         if (h->cmd_dev[q]) hipFree(h->cmd_dev[q]);
@@ -736,8 +738,8 @@ extern "C" int hsddp_simulate_policy(hsddp_handle h, int n_samples, int n_steps,
         HIPCHK(hipEventCreate(&ev[1]));
         HIPCHK(hipEventRecord(ev[0], h->stream));
     }
-    if ((rc = sync_terrain(h))) return rc;
-    launch_simulate_policy(p, h->d, a, terrain_of(h), h->stream);
+    if ((rc = sync_terrain(h)) || (rc = sync_weights(h))) return rc;
+    launch_simulate_policy(p, h->d, a, terrain_of(h), weights_of(h), h->stream);
     HIPCHK(hipGetLastError());
     if (timing) {
         float ms = 0;
@@ -1016,6 +1018,109 @@ int hsddp::sync_terrain(hsddp_handle h)
     return HSDDP_OK;
 }
 
+// ---- per-robot weights -----------------------------------------------------------------------------
+// The host rows are the source of truth (hsddp_handle.h); the kernels' copy follows by sync_weights.
+void hsddp::weights_row(const hsddp_hkd_weights &w, Wts &r)
+{
+    for (int j = 0; j < 3; ++j) { r.qbase[j] = w.q_eul[j]; r.qbase[3 + j] = w.q_pos[j]; r.qbase[6 + j] = w.q_omega[j]; r.qbase[9 + j] = w.q_v[j]; }
+    r.q_qJ = w.q_qJ;
+    for (int j = 0; j < 24; ++j) r.qf_scale[j] = w.qf_scale[j];
+    r.qf_gain = w.qf_gain; r.r_grf = w.r_grf; r.r_qJd = w.r_qJd;
+    for (int j = 0; j < 3; ++j) r.foot_w[j] = w.foot_w[j];
+    r.foot_gain = w.foot_gain; r.foot_term_cost = w.foot_term_cost; r.foot_term_grad = w.foot_term_grad;
+    r.pad[0] = r.pad[1] = 0.0;
+}
+
+bool hsddp::weights_finite(const hsddp_hkd_weights &w)
+{
+    const double *f = (const double *)&w;
+    for (int j = 0; j < NW; ++j)
+        if (!std::isfinite(f[j])) return false;
+    return true;
+}
+
+extern "C" int hsddp_set_element_weights(hsddp_handle h, const hsddp_hkd_weights *w, const int *mask)
+{
+    if (!h) return fail(HSDDP_ERR_ARG, "null handle");
+    if (!h->have_problem) return fail(HSDDP_ERR_ARG, "upload the problem first");
+    const size_t B = h->p.B;
+    if (!w) {  // the table off: every robot back at the handle's weights
+        if (h->weights.empty()) return HSDDP_OK;
+        h->weights.clear();
+        h->slots_fresh = false;
+        return HSDDP_OK;
+    }
+    for (size_t b = 0; b < B; ++b)
+        if ((!mask || mask[b]) && !weights_finite(w[b])) return fail(HSDDP_ERR_ARG, "element weights: a value is not finite");
+    if (int rc = ensure_weights_table(h)) return rc;
+    // (the iteration graphs are keyed on the table pointer: off and on find their own)
+    bool changed = h->weights.empty();
+    if (changed) h->weights.assign(B, h->desc.weights);  // robots never set read the handle's weights
+    for (size_t b = 0; b < B; ++b) {
+        if (mask && !mask[b]) continue;
+        if (std::memcmp(&h->weights[b], &w[b], sizeof w[b])) changed = true;
+        h->weights[b] = w[b];
+    }
+    if (changed) {
+        h->weights_stale = true;
+        h->slots_fresh = false;  // the stored slot costs were formed with the old weights
+    }
+    return HSDDP_OK;
+}
+
+extern "C" int hsddp_get_element_weights(hsddp_handle h, hsddp_hkd_weights *w)
+{
+    if (!h) return fail(HSDDP_ERR_ARG, "null handle");
+    if (!h->have_problem) return fail(HSDDP_ERR_ARG, "upload the problem first");
+    if (!w) return fail(HSDDP_ERR_ARG, "null output");
+    for (size_t b = 0; b < (size_t)h->p.B; ++b) w[b] = weights_of(h, b);
+    return HSDDP_OK;
+}
+
+int hsddp::ensure_weights_table(hsddp_handle h)
+{
+    if (h->weights_dev) return HSDDP_OK;
+    HIPCHK(hipSetDevice(h->desc.device));
+    // piece by piece: a call that failed half-way is taken up where it stopped, nothing allocated twice
+    if (!h->weights_pin) HIPCHK(hipHostMalloc((void **)&h->weights_pin, (size_t)h->p.B * sizeof(Wts), 0));
+    if (!h->weights_up) {
+        HIPCHK(hipEventCreateWithFlags(&h->weights_up, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(h->weights_up, h->stream));
+    }
+    return dalloc(h, h->weights_dev, (size_t)h->p.B);
+}
+
+int hsddp::sync_weights(hsddp_handle h)
+{
+    if (h->weights.empty() || !h->weights_stale) return HSDDP_OK;
+    if (!h->weights_dev) return fail(HSDDP_ERR_DEVICE, "weight rows without a device table");
+    const size_t B = h->p.B, bytes = B * sizeof(Wts);
+    HIPCHK(hipSetDevice(h->desc.device));
+    HIPCHK(hipEventSynchronize(h->weights_up));  // (the last upload has read the staging)
+    for (size_t b = 0; b < B; ++b) weights_row(h->weights[b], h->weights_pin[b]);
+    // HSDDP_WEIGHTS_TIMING=1: the upload's device time (HIP events) to stderr (a diagnostic)
+    static const bool timing = std::getenv("HSDDP_WEIGHTS_TIMING") != nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (timing) {
+        HIPCHK(hipEventCreate(&ev[0]));
+        HIPCHK(hipEventCreate(&ev[1]));
+        HIPCHK(hipEventRecord(ev[0], h->stream));
+    }
+    HIPCHK(hipMemcpyAsync(h->weights_dev, h->weights_pin, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(h->weights_up, h->stream));
+    if (timing) {
+        float ms = 0;
+        HIPCHK(hipEventRecord(ev[1], h->stream));
+        HIPCHK(hipEventSynchronize(ev[1]));
+        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        hipEventDestroy(ev[0]);
+        hipEventDestroy(ev[1]);
+        std::fprintf(stderr, "weights upload ms: %.4f (%zu bytes)\n", ms, bytes);
+    }
+    h->weights_stale = false;
+    return HSDDP_OK;
+}
+
 extern "C" int hsddp_download_trajectory(hsddp_handle h, double *Xbar, double *Ubar, double *K)
 {
     if (!h) return fail(HSDDP_ERR_ARG, "null handle");
@@ -1192,6 +1297,9 @@ extern "C" int hsddp_download_lq(hsddp_handle h, double *A, double *Bm, double *
                         bb[(12 + 3 * lg + a) * NX + 12 + 3 * lg + a] = dt * (1.0 - c[lg]);
                     }
             }
+            // the robot's weights in the kernels' form (its row, or the handle's)
+            Wts wr;
+            weights_row(weights_of(h, b), wr);
             if (l) l[o] = cost[b * S + kc + i];
             if (lx) for (int j = 0; j < NX; ++j) lx[o * NX + j] = r[LQ_LX + j];
             if (lu) for (int j = 0; j < NX; ++j) lu[o * NX + j] = r[LQ_LU + j];
@@ -1199,10 +1307,10 @@ extern "C" int hsddp_download_lq(hsddp_handle h, double *A, double *Bm, double *
                 double *m = lxx + o * NN;
                 std::fill(m, m + NN, 0.0);
                 for (int j = 0; j < NX; ++j)
-                    m[j * NX + j] = dt * (j < 12 ? p.qbase[j] : p.q_qJ * (1 - c[(j - 12) / 3]));
+                    m[j * NX + j] = dt * (j < 12 ? wr.qbase[j] : wr.q_qJ * (1 - c[(j - 12) / 3]));
                 for (int lg = 0; lg < 4; ++lg)
                     for (int a = 0; a < 3; ++a) {
-                        const double w = c[lg] ? dt * (p.foot_gain * p.foot_w[a]) : 0.0;
+                        const double w = c[lg] ? dt * (wr.foot_gain * wr.foot_w[a]) : 0.0;
                         const int pa = 3 + a, qa = 12 + 3 * lg + a;
                         m[pa * NX + pa] += w; m[qa * NX + qa] += w;
                         m[pa * NX + qa] -= w; m[qa * NX + pa] -= w;
@@ -1211,7 +1319,7 @@ extern "C" int hsddp_download_lq(hsddp_handle h, double *A, double *Bm, double *
             if (luu) {  // dt R + dt ReB Hessian of the stance legs' GRF rows (SinglePhase.cpp:380-394)
                 double *m = luu + o * NN;
                 std::fill(m, m + NN, 0.0);
-                for (int j = 0; j < NX; ++j) m[j * NX + j] = dt * (j < 12 ? p.r_grf : p.r_qJd);
+                for (int j = 0; j < NX; ++j) m[j * NX + j] = dt * (j < 12 ? wr.r_grf : wr.r_qJd);
                 static const int ix[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
                 for (int lg = 0; lg < 4; ++lg)
                     for (int a = 0; a < 3; ++a)

@@ -41,21 +41,29 @@ DEV void wave_sync()
 typedef const __attribute__((address_space(4))) Params KParams;
 DEV KParams *kparams() { return (KParams *)__builtin_amdgcn_kernarg_segment_ptr(); }
 
-// PT: Params (compile-time indices) or KParams (runtime indices)
+// PT: Params (compile-time indices), KParams (runtime indices) or a robot's row Wts (TerrT::w / ::wk)
 template <typename PT>
 DEV double q_diag(const PT &p, const int *c, int j) { return j < 12 ? p.qbase[j] : p.q_qJ * (1 - c[(j - 12) / 3]); }
-DEV double r_diag(const Params &p, int j) { return j < 12 ? p.r_grf : p.r_qJd; }
+template <typename PT>
+DEV double r_diag(const PT &p, int j) { return j < 12 ? p.r_grf : p.r_qJd; }
 template <typename PT>
 DEV double foot_weight(const PT &p, const int *c, int j) { return p.foot_gain * p.foot_w[j % 3] * c[j / 3]; }
 DEV bool touchdown(const int *c, const int *cn, int l) { return c[l] == 0 && cn[l] == 1; }
 
-// ---- per-phase terrain (hsddp_set_terrain) -----------------------------------------------------
+// ---- per-phase terrain (hsddp_set_terrain), per-robot weights (hsddp_set_element_weights) ------
 // The kernels that read the friction coefficient or the ground height end in an argument pack:
 // empty — the handle-wide Params::mu / ::ground, the arguments and the code of a handle without
 // terrain — or one pointer to the handle's [B][P] (mu, ground) pairs, read at (element, phase).
-template <bool ON>
+// The same pack ends in the handle's weight table (const Wts *, [B] rows) while that is on (WON):
+// w(p, b) is then element b's row where it is Params itself without one, so an expression names
+// its weights once (`const auto &w = terr.w(p, b); ... w.r_grf ...`) and keeps its form.  wk(b)
+// is the same for runtime field indices: the kernel-argument segment (kparams) or the row — a
+// pointer to global memory, which a runtime index never copies to scratch.
+template <bool ON, bool WON = false>
 struct TerrT {
     const double *t;
+    const Wts *wt;
+    static constexpr bool weights = WON;
     DEV double mu(const Params &p, int b, int i) const
     {
         if constexpr (ON) return t[((size_t)b * p.P + i) * 2];
@@ -66,9 +74,21 @@ struct TerrT {
         if constexpr (ON) return t[((size_t)b * p.P + i) * 2 + 1];
         else return p.ground;
     }
+    DEV const std::conditional_t<WON, Wts, Params> &w(const Params &p, size_t b) const
+    {
+        if constexpr (WON) return wt[b];
+        else return p;
+    }
+    DEV std::conditional_t<WON, const Wts, KParams> &wk(size_t b) const
+    {
+        if constexpr (WON) return wt[b];
+        else return *kparams();
+    }
 };
-DEV TerrT<false> terrain_of() { return {nullptr}; }
-DEV TerrT<true> terrain_of(const double *t) { return {t}; }
+DEV TerrT<false> terrain_of() { return {nullptr, nullptr}; }
+DEV TerrT<true> terrain_of(const double *t) { return {t, nullptr}; }
+DEV TerrT<false, true> terrain_of(const Wts *w) { return {nullptr, w}; }
+DEV TerrT<true, true> terrain_of(const double *t, const Wts *w) { return {t, w}; }
 
 // ---- the phase layout of element b ----------------------------------------------------------
 // The handle's layout (Params, read in place: runtime phase indices never index the by-value copy)
@@ -212,21 +232,25 @@ DEV double grf_value(double mu, int r, const double *f)
 // entries in order, the dt * ReB sum with min(0, min g), and their combination.  Split so that a
 // caller can bring the reference in pieces (k_rollout's slot waves), every term computed as
 // running_cost computes it.
-DEV double cost_tracking(const Params &p, const int *c, const double *x, const double *xrv)
+// (w: the knot's weights, Params or its robot's row — TerrT::w)
+template <typename WT>
+DEV double cost_tracking(const WT &p, const int *c, const double *x, const double *xrv)
 {
     double lt = 0.0;
 #pragma unroll
     for (int j = 0; j < NX; ++j) { double e = x[j] - xrv[j]; lt += e * q_diag(p, c, j) * e; }
     return lt;
 }
-DEV double cost_control(const Params &p, const double *u, const double *urv)
+template <typename WT>
+DEV double cost_control(const WT &p, const double *u, const double *urv)
 {
     double lu = 0.0;
 #pragma unroll
     for (int j = 0; j < NX; ++j) { double e = u[j] - urv[j]; lu += e * r_diag(p, j) * e; }
     return lu;
 }
-DEV double cost_foot(const Params &p, const int *c, const double *x, const double *xrv, const double *pfv)
+template <typename WT>
+DEV double cost_foot(const WT &p, const int *c, const double *x, const double *xrv, const double *pfv)
 {
     double lf = 0.0;
 #pragma unroll
@@ -287,16 +311,18 @@ DEV double cost_combine(const Params &p, const int *c, double lt, double lu, dou
 {
     lt = 0.5 * lt;
     lt += 0.5 * lu;
-    lt *= p.dt;
     lf = .5 * lf;
-    lf *= p.dt;
-    double l = lt + lf;
+    // dt lt + dt lf with the fused multiply-add spelled out: left to the compiler's contraction, the
+    // sum of two products is formed as fma(lt, dt, lf dt) in one instantiation and otherwise in
+    // another, and a robot's cost would depend on the kernel variant that evaluated it
+    double l = __builtin_fma(lt, p.dt, lf * p.dt);
     if (p.ReB_active && (c[0] + c[1] + c[2] + c[3]) > 0) l += p.dt * rc;
     return l;
 }
 
 // running cost l_k (tracking + foot regularisation + dt * ReB), and min(0, min g)
-DEV double running_cost(const Params &p, double mu, const int *c, const double *x, const double *u, const double *xr,
+template <typename WT>
+DEV double running_cost(const Params &p, const WT &w, double mu, const int *c, const double *x, const double *u, const double *xr,
                         const double *ur, const double *pf, const double *delta, const double *eps, double &viol,
                         const double *ovr = nullptr)
 {
@@ -317,7 +343,7 @@ DEV double running_cost(const Params &p, double mu, const int *c, const double *
         const d2v a = ((const d2v *)pf)[j];
         pfv[2 * j] = a.x; pfv[2 * j + 1] = a.y;
     }
-    const double lt = cost_tracking(p, c, x, xrv), lu = cost_control(p, u, urv), lf = cost_foot(p, c, x, xrv, pfv);
+    const double lt = cost_tracking(w, c, x, xrv), lu = cost_control(w, u, urv), lf = cost_foot(w, c, x, xrv, pfv);
     double mk;
     const double rc = cost_reb(p, mu, c, u, delta, eps, mk, ovr);
     viol = mk;
@@ -363,7 +389,8 @@ DEV int td_bits(const int *c, const int *cn)
 // constraint by constraint, as update_terminal_cost_with_tconstr (SinglePhase.cpp:402-411).
 // stored: the constraints' stored residuals (a TD_STALE constraint's is 0), as compute_cost reads
 // them; else h as a rollout that completes the phase computes it for every constraint.
-DEV double terminal_cost_h(const Params &p, const int *c, const double *x, const double *xr, const double *pf,
+template <typename WT>
+DEV double terminal_cost_h(const Params &p, const WT &w, const int *c, const double *x, const double *xr, const double *pf,
                            const int *mask, const double *sig, const double *lam, const double *hl, double &tviol,
                            bool stored = true)
 {
@@ -371,15 +398,15 @@ DEV double terminal_cost_h(const Params &p, const int *c, const double *x, const
 #pragma unroll
     for (int j = 0; j < NX; ++j) {
         double e = x[j] - xr[j];
-        phi += e * (p.qf_gain * p.qf_scale[j] * q_diag(p, c, j)) * e;
+        phi += e * (w.qf_gain * w.qf_scale[j] * q_diag(w, c, j)) * e;
     }
     phi *= 0.5;
 #pragma unroll
     for (int j = 0; j < 12; ++j) {
         double e = (x[12 + j] - x[3 + j % 3]) - (pf[j] - xr[3 + j % 3]);
-        fc += e * foot_weight(p, c, j) * e;
+        fc += e * foot_weight(w, c, j) * e;
     }
-    phi = phi + p.foot_term_cost * fc;
+    phi = phi + w.foot_term_cost * fc;
     double tv = 0.0;
     for (int q = 0; q < MTD; ++q) {
         const int m = mask[q];
@@ -402,14 +429,15 @@ DEV double terminal_cost_h(const Params &p, const int *c, const double *x, const
 
 // terminal cost Phi (tracking Qf + 10 * foot + AL), max |h| and h per constraint leg above the
 // phase's ground height (stored: terminal_cost_h)
-DEV double terminal_cost(const Params &p, double ground, const int *c, const double *x, const double *xr, const double *pf,
+template <typename WT>
+DEV double terminal_cost(const Params &p, const WT &w, double ground, const int *c, const double *x, const double *xr, const double *pf,
                          const int *mask, const double *sig, const double *lam, double &tviol, double *h_out,
                          bool stored)
 {
     const unsigned u = td_union(mask);
 #pragma unroll
     for (int l = 0; l < 4; ++l) h_out[l] = ((u >> l) & 1) ? hkd_foot_height_grad(l, x, nullptr) - ground : 0.0;
-    return terminal_cost_h(p, c, x, xr, pf, mask, sig, lam, h_out, tviol, stored);
+    return terminal_cost_h(p, w, c, x, xr, pf, mask, sig, lam, h_out, tviol, stored);
 }
 
 

@@ -35,6 +35,15 @@ void with_flags_table(F &&f, const T *table, Flags... flags)
     else with_flags(f, flags...);
 }
 
+// ... and with a second table after the first while it is non-null (the per-robot weight rows after
+// the terrain): f's pack is then (), (table), (second) or (table, second)
+template <typename F, typename T, typename W, typename... Flags>
+void with_flags_tables(F &&f, const T *table, const W *second, Flags... flags)
+{
+    if (second) with_flags_table([&](auto... c) { f(c..., second); }, table, flags...);
+    else with_flags_table(f, table, flags...);
+}
+
 static inline unsigned blocks_for(long n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 }  // namespace hsddp

@@ -13,7 +13,7 @@ namespace hsddp {
 // host bookkeeping), then the device rows packed at the capacity strides (S_cap state slots,
 // HSDDP_MAX_PHASES phases), every piece 16-byte aligned, the gain rows on a 128-byte line and the
 // record a whole number of lines.
-constexpr uint32_t RECORD_VERSION = 0x48454c32;  // "HEL2" (HEL1: no terrain rows in the header)
+constexpr uint32_t RECORD_VERSION = 0x48454c33;  // "HEL3" (HEL1: no terrain rows in the header; HEL2: no weight row)
 constexpr int REC_HIST = 256;  // solver-info history entries a record holds
 
 // What two handles must agree on for an element of one to continue in the other.

@@ -51,6 +51,7 @@ struct hsddp_handle_t {
         double alpha = 0;
         const int *budget = nullptr;
         const double *terrain = nullptr;
+        const hsddp::Wts *weights = nullptr;
         int par = 0;  // which host count slot (host_counter[8 + 4 * par + 1]) its copy fills
     } iter_graph[8];
     int iter_graph_next = 0;
@@ -153,7 +154,18 @@ struct hsddp_handle_t {
     double *terrain_dev = nullptr, *terrain_pin = nullptr;
     bool terrain_stale = false;
     hipEvent_t terrain_up = nullptr;
+    // per-robot weights (hsddp_set_element_weights): the host rows [B] — the source of truth; they
+    // belong to the robot, so shifts, advances and restarts leave them alone — empty: the table is
+    // off and every robot has desc.weights.  The device copy the weights instantiations read ([B]
+    // rows of Wts, allocated on first use, so the pointer the iteration graphs freeze never moves) is
+    // uploaded from pinned staging when the host rows changed (sync_weights); weights_up: that
+    // upload's event
+    std::vector<hsddp_hkd_weights> weights;
+    hsddp::Wts *weights_dev = nullptr, *weights_pin = nullptr;
+    bool weights_stale = false;
+    hipEvent_t weights_up = nullptr;
 };
+static_assert(sizeof(hsddp_hkd_weights) == hsddp::NW * sizeof(double), "hsddp_hkd_weights: NW doubles, no padding");
 
 namespace hsddp {
 
@@ -201,6 +213,7 @@ inline HorizonView view_of(hsddp_handle h)
     v.t_el = h->t_el.empty() ? nullptr : h->t_el.data();
     v.terrain = h->terrain.empty() ? nullptr : h->terrain.data();
     v.fill[0] = h->desc.cparams.mu_fric; v.fill[1] = h->desc.cparams.ground_height;
+    v.weights = h->weights.empty() ? nullptr : (const double *)h->weights.data();
     return v;
 }
 
@@ -218,6 +231,19 @@ int ensure_terrain_table(hsddp_handle h);
 // ... and the table brought up to the host rows on the handle's stream (before the launches of a
 // call that reads it; never inside a graph capture)
 int sync_terrain(hsddp_handle h);
+
+// the weight table the kernels' weights instantiations read (null: off, the plain instantiations);
+// whoever turns the table on allocates it first (ensure_weights_table), as with the terrain
+inline const Wts *weights_of(hsddp_handle h) { return h->weights.empty() ? nullptr : h->weights_dev; }
+// robot b's weights: its row, or the handle's
+inline const hsddp_hkd_weights &weights_of(hsddp_handle h, size_t b) { return h->weights.empty() ? h->desc.weights : h->weights[b]; }
+// hsddp_api.cpp: a row in the kernels' field order; the device table with its staging (allocated once);
+// the table brought up to the host rows on the handle's stream (never inside a graph capture);
+// the setter's check of one row (finite fields; negative weights are legal)
+void weights_row(const hsddp_hkd_weights &w, Wts &r);
+int ensure_weights_table(hsddp_handle h);
+int sync_weights(hsddp_handle h);
+bool weights_finite(const hsddp_hkd_weights &w);
 
 // phase of control slot kc in a layout
 inline int phase_of_control(const Layout &L, int kc)

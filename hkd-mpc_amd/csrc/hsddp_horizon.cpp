@@ -880,6 +880,16 @@ static int move_elements(hsddp_handle dst, const MoveSource &src, int n, const i
         }
     }
     if (brings_terrain && (rc = ensure_terrain_table(dst))) return rc;
+    // ... and its weight row hsddp_set_element_weights' check
+    bool brings_weights = false;
+    for (int m = 0; m < n; ++m) {
+        if (!in[m].has_weights) continue;
+        brings_weights = true;
+        hsddp_hkd_weights w;
+        std::memcpy(&w, in[m].weights, sizeof w);
+        if (!weights_finite(w)) return fail(HSDDP_ERR_ARG, "an element's weight row holds a non-finite value");
+    }
+    if (brings_weights && (rc = ensure_weights_table(dst))) return rc;
     if (restride && !kd.has_table)
         return fail(HSDDP_ERR_UNSUPPORTED, "the move changes the destination's strides: its other elements' references "
                                            "are rebuilt from the table, and it has none");
@@ -1001,6 +1011,17 @@ static int move_elements(hsddp_handle dst, const MoveSource &src, int n, const i
                                  &dst->terrain[(size_t)list[m] * p.P * 2]);
             dst->terrain_stale = true;
         }
+    }
+    // the weight rows arrive with the robots (from a handle with the table off: that handle's weights,
+    // which are the destination's — compatible()); a destination with the table off turns it on when a
+    // robot brings a row, its residents reading its desc.weights
+    if (brings_weights && dst->weights.empty()) dst->weights.assign((size_t)B, dst->desc.weights);
+    if (!dst->weights.empty()) {
+        for (int m = 0; m < n; ++m) {
+            if (in[m].has_weights) std::memcpy(&dst->weights[list[m]], in[m].weights, sizeof(hsddp_hkd_weights));
+            else dst->weights[list[m]] = dst->desc.weights;
+        }
+        dst->weights_stale = true;
     }
     // the windows (at a new stride every element's references are rebuilt; the arriving elements'
     // rows then replace theirs) and the clocks

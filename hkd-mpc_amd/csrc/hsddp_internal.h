@@ -20,6 +20,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include "hkd_model.h"
 #include "hsddp_phases.h"
 
@@ -112,6 +113,17 @@ struct Params {
     // (trials, accepted, the sweep's regularisation) of its inner iteration in Bufs::dbg (k_decide)
     int trace;
 };
+
+// One robot's HKD weights (hsddp_set_element_weights): a row of the handle's device table [B], the
+// weight fields of Params in Params' order, padded to three 128-byte lines.  The kernels' weights
+// instantiations read element b's row where the plain ones read Params (TerrT::w / ::wk, hsddp_device.h).
+struct Wts {
+    double qbase[12], q_qJ, qf_scale[24], qf_gain, r_grf, r_qJd, foot_w[3], foot_gain, foot_term_cost, foot_term_grad;
+    double pad[2];
+};
+static_assert(sizeof(Wts) == 48 * sizeof(double), "Wts: three 128-byte lines");
+static_assert(offsetof(Params, foot_term_grad) - offsetof(Params, qbase) == offsetof(Wts, foot_term_grad),
+              "Wts: Params' weight fields in Params' order");
 
 // one element deferred to the parallel retry: its index and the regularisation of its failed sweep
 struct RetryEntry {
@@ -237,21 +249,25 @@ struct Bufs {
 // or null: Params::mu / ::ground for every phase, the instantiations and arguments without terrain.
 // Not in Bufs: the kernels that never read it (the sweep, the linear rollout, the shift, ...) keep
 // their argument segments
+//
+// weights: the per-robot weight rows [B] (hsddp_set_element_weights; the weights instantiations,
+// which read element b's row wherever the plain ones read Params' weight fields), or null: the
+// handle's weights in Params, the instantiations and arguments without rows.  Not in Bufs either.
 
 // ---- hsddp_lq.hip: the LQ model (k_lq) and the terminal tasks (k_terminal) ----
-void launch_lq(const Params &p, const Bufs &d, const double *terrain, hipStream_t st);
+void launch_lq(const Params &p, const Bufs &d, const double *terrain, const Wts *weights, hipStream_t st);
 
 // ---- hsddp_sweep.hip, hsddp_linear.hip ----
-void launch_riccati(const Params &p, const Bufs &d, hipStream_t st);
-void launch_lin_rollout(const Params &p, const Bufs &d, hipStream_t st);
+void launch_riccati(const Params &p, const Bufs &d, const Wts *weights, hipStream_t st);
+void launch_lin_rollout(const Params &p, const Bufs &d, const Wts *weights, hipStream_t st);
 
 // ---- hsddp_rollout.hip: the forward line search ----
 // tix: the trial's index in the inner iteration's line search (-1: the initial rollout)
 // (last: this trial is the search's last step size — used when the rollout launch also decides)
 void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
-                    const double *terrain, hipStream_t st);
+                    const double *terrain, const Wts *weights, hipStream_t st);
 void launch_decide(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
-                   const double *terrain, hipStream_t st);
+                   const double *terrain, const Wts *weights, hipStream_t st);
 
 // ---- hsddp_outer.hip: the outer loop's updates and the element-state housekeeping ----
 // nominal rows of every element into buffer 0 (Bufs::sel bit 0 cleared), for host transfers

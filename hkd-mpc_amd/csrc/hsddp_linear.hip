@@ -122,18 +122,24 @@ DEV double pick(const double (&a)[N], int i)
 
 // q_diag / foot_weight (hsddp_device.h) with the lane-dependent indices resolved by selects:
 // a lane-indexed read of a kernel-argument array is a memory round trip
-template <typename real>
-DEV void lxx_row(const Params &p, const PhaseConst<real> &pc, int r, LxxRow<real> &L)
+// ww: the element's weights, Params or its row (TerrT::w) — a row's entry is read at its runtime
+// index (global memory; never copied to scratch)
+template <typename real, typename WT>
+DEV void lxx_row(const Params &p, const WT &ww, const PhaseConst<real> &pc, int r, LxxRow<real> &L)
 {
+    auto at = [&](const auto &a, int i) {
+        if constexpr (std::is_same_v<WT, Params>) return pick(a, i);
+        else return a[i];
+    };
     L.diag = 0.0; L.xp = 0.0;
 #pragma unroll
     for (int l = 0; l < 4; ++l) L.xq[l] = 0.0;
     if (r >= NX) return;
-    double dg = p.dt * (r < 12 ? pick(p.qbase, r) : p.q_qJ * (1 - contact(pc, (r - 12) / 3)));
+    double dg = p.dt * (r < 12 ? at(ww.qbase, r) : ww.q_qJ * (1 - contact(pc, (r - 12) / 3)));
     if (r >= 3 && r < 6) {
         // dt c^2 (foot_gain w c) = dt foot_gain w for c = 1, else 0 (selects: no per-phase
         // conversions kept live across the knot loop)
-        const double fw = p.dt * (p.foot_gain * pick(p.foot_w, r - 3));
+        const double fw = p.dt * (ww.foot_gain * at(ww.foot_w, r - 3));
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
             const double w = pc.c[l] ? fw : 0.0;
@@ -142,7 +148,7 @@ DEV void lxx_row(const Params &p, const PhaseConst<real> &pc, int r, LxxRow<real
         }
     } else if (r >= 12) {
         const int m = r - 12;
-        const double w = contact(pc, m / 3) ? p.dt * (p.foot_gain * pick(p.foot_w, m % 3)) : 0.0;
+        const double w = contact(pc, m / 3) ? p.dt * (ww.foot_gain * at(ww.foot_w, m % 3)) : 0.0;
         dg += w;
         L.xp = -w;
     }
@@ -464,9 +470,12 @@ DEV void lin_knot(const Params &p, LinVec<real> &S, LinBuf<real> &cur, LinBuf<re
     LSTAMP(4);
 }
 
-template <typename real, bool EL>
-__global__ __launch_bounds__(64, 2) void k_lin_rollout(Params p, Bufs d)
+// wp: the weight table (hsddp_set_element_weights), or nothing: Params' weights, today's arguments
+// and code (TerrT, hsddp_device.h)
+template <typename real, bool EL, typename... WP>
+__global__ __launch_bounds__(64, 2) void k_lin_rollout(Params p, Bufs d, WP... wp)
 {
+    const auto wt = terrain_of(wp...);
     __shared__ LinVec<real> S;
     __shared__ LinBuf<real> B0;
     __shared__ LinBuf<real> B1;
@@ -527,8 +536,8 @@ __global__ __launch_bounds__(64, 2) void k_lin_rollout(Params p, Bufs d)
         if (rowl) dx = dx + defg[(b * p.S + s0) * NX + r];
         if (st) d.dX[(b * p.S + s0) * NX + r] = dx;
         // lxx row r (HKDCost.cpp:32): diagonal + foot cross terms
-        lxx_row(p, R.pc, r, R.lx);
-        R.ru = rowl ? (real)(p.dt * r_diag(p, r)) : (real)0;
+        lxx_row(p, wt.w(p, b), R.pc, r, R.lx);
+        R.ru = rowl ? (real)(p.dt * r_diag(wt.w(p, b), r)) : (real)0;
         // control r has a gain row only when its B column is non-zero (KCW layout)
         const bool stl = contact(R.pc, (rr % HC) / 3) != 0;
         R.cpl = rowl && (rr < HC ? stl : !stl);
@@ -562,14 +571,13 @@ __global__ __launch_bounds__(64, 2) void k_lin_rollout(Params p, Bufs d)
 #endif
     if (r == 0 && act) merit_step(p, E, v1, v2);
 }
-
-void launch_lin_rollout(const Params &p, const Bufs &d, hipStream_t st)
+void launch_lin_rollout(const Params &p, const Bufs &d, const Wts *weights, hipStream_t st)
 {
     const dim3 g((unsigned)(p.elem_layout ? p.n_pairs : (p.B + 1) / 2));
-    with_flags([&](auto f32, auto el) {
+    with_flags_table([&](auto f32, auto el, auto... wp) {
         using real = std::conditional_t<decltype(f32)::value, float, double>;
-        hipLaunchKernelGGL((k_lin_rollout<real, decltype(el)::value>), g, dim3(64), 0, st, p, d);
-    }, p.fp32, p.elem_layout);
+        hipLaunchKernelGGL((k_lin_rollout<real, decltype(el)::value>), g, dim3(64), 0, st, p, d, wp...);
+    }, weights, p.fp32, p.elem_layout);
 }
 
 }  // namespace hsddp

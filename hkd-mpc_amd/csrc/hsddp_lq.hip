@@ -168,11 +168,13 @@ DEV void terminal_task(const Params &p, const Bufs &d, const TR &terr, TermLds &
         sh[l] = h;
     }
     wave_sync();
-    KParams &kp = *kparams();  // runtime-indexed weights
+    // the robot's weights: Params / its row for compile-time fields, runtime-indexed ones in place
+    const auto &w = terr.w(p, b);
+    const auto &kp = terr.wk(b);
     double *rec = d.term + ((size_t)b * p.P + i) * TW;
     if (t == 0) {  // the phase's terminal cost at X[N] (SinglePhase::compute_cost's last term) for k_lq's slot sums
         double tv;
-        d.slot_cost[(size_t)b * p.S + s] = terminal_cost_h(p, sc, sx, sxr, spf, smask, ssl, ssl + MTD * 4, sh, tv);
+        d.slot_cost[(size_t)b * p.S + s] = terminal_cost_h(p, w, sc, sx, sxr, spf, smask, ssl, ssl + MTD * 4, sh, tv);
     }
     if (t < NX) { // Phix
         const int j = t;
@@ -181,12 +183,12 @@ DEV void terminal_task(const Params &p, const Bufs &d, const TR &terr, TermLds &
             for (int l = 0; l < 4; ++l) {
                 int m = 3 * l + (j - 3);
                 double e = (sx[12 + m] - sx[j]) - (spf[m] - sxr[j]);
-                v += -(p.foot_term_grad * sc[l] * foot_weight(kp, sc, m) * e);
+                v += -(w.foot_term_grad * sc[l] * foot_weight(kp, sc, m) * e);
             }
         } else if (j >= 12) {
             int m = j - 12, l = m / 3;
             double e = (sx[j] - sx[3 + m % 3]) - (spf[m] - sxr[3 + m % 3]);
-            v += p.foot_term_grad * sc[l] * foot_weight(kp, sc, m) * e;
+            v += w.foot_term_grad * sc[l] * foot_weight(kp, sc, m) * e;
         }
         for (int l = 0; l < 4; ++l) v += scoef[l][0] * shx[l][j];
         rec[TM_PHIX + j] = v;
@@ -196,7 +198,7 @@ DEV void terminal_task(const Params &p, const Bufs &d, const TR &terr, TermLds &
     // Lane r < 24 forms diagonal entry r, lane m < 12 also the weight of joint column 12 + m
     // (runtime-indexed weights read once per phase, not once per entry); the 576 entries then
     // combine them.
-    auto fw = [&](int l, int j) { return p.foot_term_grad * sc[l] * sc[l] * foot_weight(kp, sc, 3 * l + j); };
+    auto fw = [&](int l, int j) { return w.foot_term_grad * sc[l] * sc[l] * foot_weight(kp, sc, 3 * l + j); };
     double *sdd = S.sdw, *scw = S.sdw + NX;  // (the trig is dead: read before the last wave_sync)
     if (t < NX) {
         const int r = t;
@@ -242,11 +244,12 @@ DEV void terminal_task(const Params &p, const Bufs &d, const TR &terr, TermLds &
 
 // lu + ReB gradient / Hessian of one knot (SinglePhase.cpp:380-394); the GRF constraint values from
 // the control row's forces, or the older ones ovr (constraint_forces)
-DEV void lq_lu_reb(const Params &p, double mu, const int *c, const double *u, const double *ovr, const double *ur, const double *dl,
+template <typename WT>
+DEV void lq_lu_reb(const Params &p, const WT &w, double mu, const int *c, const double *u, const double *ovr, const double *ur, const double *dl,
                    const double *ep, double *lu, double *rb)
 {
 #pragma unroll
-    for (int j = 0; j < NU; ++j) lu[j] = p.dt * r_diag(p, j) * (u[j] - ur[j]);
+    for (int j = 0; j < NU; ++j) lu[j] = p.dt * r_diag(w, j) * (u[j] - ur[j]);
 #pragma unroll
     for (int j = 0; j < 24; ++j) rb[j] = 0.0;
     // uniform ReB parameters (the default schedule) and per-knot ones as separate code: in the
@@ -303,7 +306,7 @@ DEV void terminal_wave(const Params &p, const Bufs &d, const TR &terr, TermLds *
 // The A - I / B pieces go out by direct stores (staging them would keep all 102 values live).
 // SLOTS: the slot costs and |Defect|^2 are recomputed (Params::lq_slots; instantiated apart so the
 // common path keeps the registers the cost code would take)
-// tr: the terrain table, or nothing (TerrT, hsddp_device.h)
+// tr: the terrain table and / or the weight table, or nothing (TerrT, hsddp_device.h)
 template <bool F32, bool EL, bool SLOTS, typename... TR>
 __global__ __launch_bounds__(256, FWD_MINB) void k_lq(Params p, Bufs d, TR... tr)
 {
@@ -375,9 +378,10 @@ __global__ __launch_bounds__(256, FWD_MINB) void k_lq(Params p, Bufs d, TR... tr
     const double *ur = ref_ptr(p, d.ref_u, b, s, NU);
     const double *dl = d.reb_delta + ((size_t)b * p.Kc + kc) * 20, *ep = d.reb_eps + ((size_t)b * p.Kc + kc) * 20;
     const double mu = terr.mu(p, b, i);
+    const auto &wr = terr.w(p, b);  // the robot's weights
     if (SLOTS) {  // the running cost (else the last rollout's: same trajectory, same parameters)
         double viol;
-        d.slot_cost[(size_t)b * p.S + s] = running_cost(p, mu, c, x, u, xr, ur, pf, dl, ep, viol, ovr);
+        d.slot_cost[(size_t)b * p.S + s] = running_cost(p, wr, mu, c, x, u, xr, ur, pf, dl, ep, viol, ovr);
     }
 
     // the record in the solver's Riccati precision (fp64, or fp32 in config C5's mode)
@@ -414,11 +418,11 @@ __global__ __launch_bounds__(256, FWD_MINB) void k_lq(Params p, Bufs d, TR... tr
     {
         double lx[NX];
 #pragma unroll
-        for (int j = 0; j < NX; ++j) lx[j] = p.dt * q_diag(p, c, j) * (x[j] - xr[j]);
+        for (int j = 0; j < NX; ++j) lx[j] = p.dt * q_diag(wr, c, j) * (x[j] - xr[j]);
 #pragma unroll
         for (int j = 0; j < 12; ++j) {
             double e = (x[12 + j] - x[3 + j % 3]) - (pf[j] - xr[3 + j % 3]);
-            double v = p.dt * c[j / 3] * foot_weight(p, c, j) * e;
+            double v = p.dt * c[j / 3] * foot_weight(wr, c, j) * e;
             lx[3 + j % 3] += -v;
             lx[12 + j] += v;
         }
@@ -427,7 +431,7 @@ __global__ __launch_bounds__(256, FWD_MINB) void k_lq(Params p, Bufs d, TR... tr
     }
     // lu + ReB gradient / Hessian (SinglePhase.cpp:380-394)
     double lu[NU], rb[24];
-    lq_lu_reb(p, mu, c, u, ovr, ur, dl, ep, lu, rb);
+    lq_lu_reb(p, wr, mu, c, u, ovr, ur, dl, ep, lu, rb);
 #pragma unroll
     for (int j = 0; j < NU; ++j) put(LQ_LU + j, lu[j]);
 #pragma unroll
@@ -452,7 +456,7 @@ __global__ __launch_bounds__(128, 4) void k_terminal(Params p, Bufs d, TR... tr)
     terminal_wave<EL>(p, d, terrain_of(tr...), S + w * TERM_TPW, (long)blockIdx.x * 2 + w, threadIdx.x & 63);
 }
 
-void launch_lq(const Params &p, const Bufs &d, const double *terrain, hipStream_t st)
+void launch_lq(const Params &p, const Bufs &d, const double *terrain, const Wts *weights, hipStream_t st)
 {
     // the terminal waves: a launch of their own (five waves per SIMD), or, for a small batch whose
     // knot and terminal blocks all fit the chip at once (C1: one robot), the blocks after k_lq's
@@ -462,15 +466,15 @@ void launch_lq(const Params &p, const Bufs &d, const double *terrain, hipStream_
     const bool by_knot = !p.lq_slots && !p.fp32;  // k_lq's grid: control knots or state slots
     if (!merged) {
         const unsigned nt2 = blocks_for((long)p.B * p.P, 2 * TERM_TPW);
-        with_flags_table([&](auto el, auto... tr) {
+        with_flags_tables([&](auto el, auto... tr) {
             hipLaunchKernelGGL(k_terminal<decltype(el)::value>, dim3(nt2), dim3(128), 0, st, p, d, tr...);
-        }, terrain, p.elem_layout);
+        }, terrain, weights, p.elem_layout);
     }
     const dim3 g(blocks_for((long)p.B * (by_knot ? p.Kc : p.S), 256) + (merged ? nterm : 0));
-    with_flags_table([&](auto f32, auto el, auto slots, auto... tr) {
+    with_flags_tables([&](auto f32, auto el, auto slots, auto... tr) {
         hipLaunchKernelGGL((k_lq<decltype(f32)::value, decltype(el)::value, decltype(slots)::value>), g, dim3(256), 0, st, p, d,
                            tr...);
-    }, terrain, p.fp32, p.elem_layout, p.lq_slots);
+    }, terrain, weights, p.fp32, p.elem_layout, p.lq_slots);
 }
 
 }  // namespace hsddp

@@ -545,6 +545,8 @@ void export_element(const HorizonView &v, int b, ElementImport &out)
     out.clock = v.t_el ? v.t_el[b] : v.t_cur;
     out.has_terrain = v.terrain ? 1 : 0;
     if (v.terrain) std::copy_n(&v.terrain[(size_t)b * v.P * 2], L.P * 2, out.terrain);
+    out.has_weights = v.weights ? 1 : 0;
+    if (v.weights) std::copy_n(&v.weights[(size_t)b * NW], NW, out.weights);
 }
 
 int plan_import_batch(const HorizonView &v, const std::vector<int> &list, const ElementImport *in, RestartBatch &r,

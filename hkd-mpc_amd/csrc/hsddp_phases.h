@@ -125,6 +125,7 @@ struct HorizonView {
     const float *t_el;      // [B] each element's own (null: t_cur)
     const double *terrain;  // [B][P][2] (mu, ground) per phase (hsddp_set_terrain), or null: off
     double fill[2];         // the handle's cparams pair: the row of a phase without one of its own
+    const double *weights;  // [B][NW] per-robot weight rows (hsddp_set_element_weights), or null: off
 
     const Layout &layout(int b) const { return lays ? lays[b] : *shared; }
     const int *reach_of(int b) const { return lays ? reach + (size_t)b * MAXP : reach; }
@@ -265,6 +266,7 @@ void put_restart_rows(const RestartPlan &plan, int P, int *contacts, double *dur
 // What the host holds of one element between ticks, as an element record carries it: layout, reach
 // flags, contact rows 0 .. P, contact durations (zero without a reference table), window start and
 // QuadReference clock.  Rows past the element's phases are zero.
+constexpr int NW = 46;  // doubles of one hsddp_hkd_weights (include/hsddp.h)
 struct ElementImport {
     Layout L;
     int reach[MAXP];
@@ -274,6 +276,8 @@ struct ElementImport {
     float clock;
     int has_terrain;              // the source's terrain was on: terrain holds the element's rows
     double terrain[MAXP * 2];     // (mu, ground) per phase
+    int has_weights;              // the source's weight table was on: weights holds the robot's row
+    double weights[NW];           // (the fields of hsddp_hkd_weights, in order)
 };
 // element b of the view
 void export_element(const HorizonView &v, int b, ElementImport &out);

@@ -58,7 +58,9 @@ DEV void finish_defect(const Params &p, const Bufs &d, int b, int s, int k, cons
 // the terminal cost of phase i at its last slot s (x = X[N]) with its violation and touchdown
 // residuals; stored: with the constraints' stored residuals (a phase the rollout did not complete),
 // else as a rollout completing the phase computes them; ground: the phase's ground height
-DEV void finish_terminal(const Params &p, const Bufs &d, double ground, int b, int s, int i, const int *c, const int *cn, const double *x,
+// w: the robot's weights (TerrT::w)
+template <typename WT>
+DEV void finish_terminal(const Params &p, const Bufs &d, const WT &w, double ground, int b, int s, int i, const int *c, const int *cn, const double *x,
                          bool stored = false)
 {
     const size_t sb = (size_t)b * p.S;
@@ -66,7 +68,7 @@ DEV void finish_terminal(const Params &p, const Bufs &d, double ground, int b, i
     double tv, h[4];
     const size_t q = ((size_t)b * p.P + i) * MTD;
     (void)cn;
-    d.slot_cost[sb + s] = terminal_cost(p, ground, c, x, xr, pf, d.td_mask + q, d.al_sigma + q * 4, d.al_lambda + q * 4, tv, h,
+    d.slot_cost[sb + s] = terminal_cost(p, w, ground, c, x, xr, pf, d.td_mask + q, d.al_sigma + q * 4, d.al_lambda + q * 4, tv, h,
                                         stored);
     d.slot_viol[sb + s] = tv;
 #pragma unroll
@@ -76,15 +78,15 @@ DEV void finish_terminal(const Params &p, const Bufs &d, double ground, int b, i
 // the running cost of control slot kc = k0(i) + k at state slot s, mu its phase's friction
 // coefficient; COLS: the reference from the entry-major copy (Bufs::ref_t: lanes on consecutive slots
 // read contiguous pieces)
-template <bool COLS = false>
-DEV void finish_running(const Params &p, const Bufs &d, double mu, int b, int s, int kc, const int *c, const double *x, const double *u)
+template <bool COLS = false, typename WT>
+DEV void finish_running(const Params &p, const Bufs &d, const WT &w, double mu, int b, int s, int kc, const int *c, const double *x, const double *u)
 {
     if constexpr (COLS) {
         const double *dl = d.reb_delta + ((size_t)b * p.Kc + kc) * 20, *ep = d.reb_eps + ((size_t)b * p.Kc + kc) * 20;
         alignas(16) double xr[NX], ur[NU], pf[12];
         ref_from_cols(p, d, b, s, xr, ur, pf);
         double viol;
-        d.slot_cost[(size_t)b * p.S + s] = running_cost(p, mu, c, x, u, xr, ur, pf, dl, ep, viol);
+        d.slot_cost[(size_t)b * p.S + s] = running_cost(p, w, mu, c, x, u, xr, ur, pf, dl, ep, viol);
         d.slot_viol[(size_t)b * p.S + s] = viol;
         return;
     }
@@ -93,7 +95,7 @@ DEV void finish_running(const Params &p, const Bufs &d, double mu, int b, int s,
     const double *ur = ref_ptr(p, d.ref_u, b, s, NU);
     const double *dl = d.reb_delta + ((size_t)b * p.Kc + kc) * 20, *ep = d.reb_eps + ((size_t)b * p.Kc + kc) * 20;
     double viol;
-    d.slot_cost[sb + s] = running_cost(p, mu, c, x, u, xr, ur, pf, dl, ep, viol);
+    d.slot_cost[sb + s] = running_cost(p, w, mu, c, x, u, xr, ur, pf, dl, ep, viol);
     d.slot_viol[sb + s] = viol;
 }
 
@@ -103,9 +105,9 @@ DEV void finish_slot(const Params &p, const Bufs &d, const TR &terr, const L_ &L
 {
     finish_defect(p, d, b, s, k, x, xs);
     if (k == L.N(i))
-        finish_terminal(p, d, terr.ground(p, b, i), b, s, i, c, cn, x);
+        finish_terminal(p, d, terr.w(p, b), terr.ground(p, b, i), b, s, i, c, cn, x);
     else
-        finish_running(p, d, terr.mu(p, b, i), b, s, L.k0(i) + k, c, x, u);
+        finish_running(p, d, terr.w(p, b), terr.mu(p, b, i), b, s, L.k0(i) + k, c, x, u);
 }
 
 // trial tix > 0 of an inner iteration runs only when an element is still searching after trial
@@ -272,7 +274,7 @@ DEV void rollout_boundary(const Params &p, const Bufs &d, const TR &terr, double
         finish_defect(p, d, b, s0, 0, x, xs);
     }
     trial(sN, x);
-    finish_terminal(p, d, terr.ground(p, b, i), b, sN, i, c, cn, x);
+    finish_terminal(p, d, terr.w(p, b), terr.ground(p, b, i), b, sN, i, c, cn, x);
 }
 
 // WIDE: p.S >= RW (instantiated apart: a wave's 64 slots then belong to at most two elements, and
@@ -366,7 +368,7 @@ DEV void rollout_block(const Params &p, const Bufs &d, const TR &terr, double ep
         d2 *ug = (d2 *)(kubuf(tb) + kq * NU);
 #pragma unroll
         for (int j = 0; j < NU / 2; ++j) ug[j] = d2{u[2 * j], u[2 * j + 1]};
-        finish_running<true>(p, d, terr.mu(p, b, i), b, s, L.k0(i) + k, c, x, u);
+        finish_running<true>(p, d, terr.w(p, b), terr.mu(p, b, i), b, s, L.k0(i) + k, c, x, u);
     }
     RSTAMP(4);
     // u_prev: the previous slot's control row is the previous lane's (k > 0: slot s - 1 is a
@@ -545,7 +547,7 @@ DEV void ss_phase(const Params &p, const Bufs &d, const TR &terr, int b, int i, 
         for (int j = 0; j < NX; ++j) xg[j] = x[j];
         if (k > 0 || x_init) finish_defect(p, d, b, s, k, x, k > 0 ? xs : x);
         if (k == N) {
-            finish_terminal(p, d, terr.ground(p, b, i), b, s, i, c, cn, x);
+            finish_terminal(p, d, terr.w(p, b), terr.ground(p, b, i), b, s, i, c, cn, x);
             break;
         }
         // U = Ubar + eps dU + K (X - Xbar) (SinglePhase.cpp:200), K from the 12 coupled gain rows
@@ -562,7 +564,7 @@ DEV void ss_phase(const Params &p, const Bufs &d, const TR &terr, int b, int i, 
         }
         double *ug = U + (kb + kc) * NU;
         for (int j = 0; j < NU; ++j) { u[j] = add_step(ub[j], eps, du[j]) + u[j]; ug[j] = u[j]; }
-        finish_running(p, d, terr.mu(p, b, i), b, s, kc, c, x, u);
+        finish_running(p, d, terr.w(p, b), terr.mu(p, b, i), b, s, kc, c, x, u);
         hkd_step(x, u, cd, p.dt, xs);
     }
 }
@@ -664,7 +666,7 @@ DEV void diverged_fixup(const Params &p, const Bufs &d, const TR &terr, const La
         // kernel's registers; the arithmetic is the slot kernels')
         const double *x = XT + (sb + s) * NX;
         if (k == L.N(ip)) {
-            finish_terminal(p, d, terr.ground(p, b, ip), b, s, ip, c, cn, x, true);
+            finish_terminal(p, d, terr.w(p, b), terr.ground(p, b, ip), b, s, ip, c, cn, x, true);
             continue;
         }
         const int kc = L.k0(ip) + k;
@@ -674,7 +676,7 @@ DEV void diverged_fixup(const Params &p, const Bufs &d, const TR &terr, const La
         const double *ur = ref_ptr(p, d.ref_u, b, s, NU);
         const double *dl = d.reb_delta + (kq + kc) * 20, *ep = d.reb_eps + (kq + kc) * 20;
         double viol;
-        d.slot_cost[sb + s] = running_cost(p, terr.mu(p, b, ip), c, x, u, xr, ur, pf, dl, ep, viol, ovr);
+        d.slot_cost[sb + s] = running_cost(p, terr.w(p, b), terr.mu(p, b, ip), c, x, u, xr, ur, pf, dl, ep, viol, ovr);
         d.slot_viol[sb + s] = viol;
     }
 }
@@ -858,36 +860,36 @@ static bool fused_decide(const Params &p)
 }
 
 void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
-                    const double *terrain, hipStream_t st)
+                    const double *terrain, const Wts *weights, hipStream_t st)
 {
     if (p.ms0) {  // single shooting: every knot simulated (k_rollout_ss)
-        with_flags_table([&](auto el, auto... tr) {
+        with_flags_tables([&](auto el, auto... tr) {
             hipLaunchKernelGGL(k_rollout_ss<decltype(el)::value>, dim3((p.B + 3) / 4), dim3(64), 0, st, p, d, eps, init, tix, tr...);
-        }, terrain, p.elem_layout);
+        }, terrain, weights, p.elem_layout);
         return;
     }
     // slot waves, then the phase-boundary waves (k_rollout, rollout_boundary)
     const dim3 g(blocks_for((long)p.B * p.S, 64) + blocks_for((long)p.B * p.P, 64));
     const bool wide = p.S >= RW;  // (rollout_block)
-    with_flags_table([&](auto el, auto fuse, auto wd, auto... tr) {
+    with_flags_tables([&](auto el, auto fuse, auto wd, auto... tr) {
         hipLaunchKernelGGL((k_rollout<decltype(el)::value, decltype(fuse)::value, decltype(wd)::value>), g, dim3(64), 0, st, p, d,
                            eps, init, tix, last, budget, tr...);
-    }, terrain, p.elem_layout, fused_decide(p), wide);
+    }, terrain, weights, p.elem_layout, fused_decide(p), wide);
     // (a fused launch has no tail: fused_decide)
     if (p.has_tail)
-        with_flags_table([&](auto el, auto... tr) {
+        with_flags_tables([&](auto el, auto... tr) {
             hipLaunchKernelGGL(k_rollout_tail<decltype(el)::value>, dim3((p.B + 63) / 64), dim3(64), 0, st, p, d, eps, init, tix,
                                tr...);
-        }, terrain, p.elem_layout);
+        }, terrain, weights, p.elem_layout);
 }
 void launch_decide(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
-                   const double *terrain, hipStream_t st)
+                   const double *terrain, const Wts *weights, hipStream_t st)
 {
     if (fused_decide(p)) return;  // decided by the rollout launch
-    with_flags_table([&](auto el, auto... tr) {
+    with_flags_tables([&](auto el, auto... tr) {
         hipLaunchKernelGGL(k_decide<decltype(el)::value>, dim3((p.B + 3) / 4), dim3(64), 0, st, p, d, eps, last, init, tix, budget,
                            tr...);
-    }, terrain, p.elem_layout);
+    }, terrain, weights, p.elem_layout);
 }
 
 }  // namespace hsddp

@@ -35,7 +35,7 @@ struct KnotAt {
     int i, k, s;
 };
 
-// tr: the terrain table, or nothing (TerrT, hsddp_device.h)
+// tr: the terrain table and / or the weight table, or nothing (TerrT, hsddp_device.h)
 template <bool EL, typename... TR>
 __global__ __launch_bounds__(64) void k_simulate_policy(Params p, Bufs d, SimArgs a, TR... tr)
 {
@@ -141,7 +141,8 @@ __global__ __launch_bounds__(64) void k_simulate_policy(Params p, Bufs d, SimArg
                 live = false;
             } else {
                 const double *xr = sh + PK_XR, *ur = sh + PK_UR, *pf = sh + PK_PF;
-                const double lt = cost_tracking(p, c, x, xr), lu = cost_control(p, u, ur), lf = cost_foot(p, c, x, xr, pf);
+                const auto &w = terr.w(p, b);  // the robot's weights
+                const double lt = cost_tracking(w, c, x, xr), lu = cost_control(w, u, ur), lf = cost_foot(w, c, x, xr, pf);
                 cost += cost_combine(p, c, lt, lu, lf, 0.0);  // (no ReB term)
                 const double mu = terr.mu(p, b, i);
 #pragma unroll
@@ -159,7 +160,7 @@ __global__ __launch_bounds__(64) void k_simulate_policy(Params p, Bufs d, SimArg
                     const int none[MTD] = {0, 0, 0, 0};  // (no AL term)
                     double tv;
                     const double ground = terr.ground(p, b, i);
-                    cost += terminal_cost_h(p, c, x, xe, pe, none, nullptr, nullptr, nullptr, tv);
+                    cost += terminal_cost_h(p, w, c, x, xe, pe, none, nullptr, nullptr, nullptr, tv);
 #pragma unroll
                     for (int l = 0; l < 4; ++l)
                         if (touchdown(c, cn, l)) max_td = fmax(max_td, fabs(hkd_foot_height_grad(l, x, nullptr) - ground));
@@ -182,12 +183,13 @@ __global__ __launch_bounds__(64) void k_simulate_policy(Params p, Bufs d, SimArg
     }
 }
 
-void launch_simulate_policy(const Params &p, const Bufs &d, const SimArgs &a, const double *terrain, hipStream_t st)
+void launch_simulate_policy(const Params &p, const Bufs &d, const SimArgs &a, const double *terrain, const Wts *weights,
+                            hipStream_t st)
 {
     const unsigned grid = (unsigned)p.B * (unsigned)((a.M + 63) / 64);
-    with_flags_table([&](auto el, auto... tr) {
+    with_flags_tables([&](auto el, auto... tr) {
         hipLaunchKernelGGL(k_simulate_policy<decltype(el)::value>, dim3(grid), dim3(64), 0, st, p, d, a, tr...);
-    }, terrain, p.elem_layout);
+    }, terrain, weights, p.elem_layout);
 }
 
 }  // namespace hsddp

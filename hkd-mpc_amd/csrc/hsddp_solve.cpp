@@ -88,7 +88,8 @@ static int solve_check(hsddp_handle h)
     if (h->need_inputs) return fail(HSDDP_ERR_ARG, "the layout changed (hsddp_shift): call hsddp_update_problem first");
     HIPCHK(hipSetDevice(h->desc.device));
     h->sim_fresh = false;  // the policy changes: a simulation held is of the old one
-    return sync_terrain(h);
+    if (int rc = sync_terrain(h)) return rc;
+    return sync_weights(h);
 }
 
 static std::vector<double> ls_steps(double alpha)
@@ -113,8 +114,8 @@ static void begin_launches(hsddp_handle h)
     if (h->p.trace) hipMemsetAsync(h->d.dbg, 0, (size_t)h->p.B * 16 * sizeof(unsigned long long), h->stream);
     sync_ref_columns(h);
     launch_reset_elements(h->p, h->d, h->stream);
-    launch_rollout(h->p, h->d, 0.0, 0, 1, -1, budget_of(h), terrain_of(h), h->stream);
-    launch_decide(h->p, h->d, 0.0, 0, 1, -1, budget_of(h), terrain_of(h), h->stream);
+    launch_rollout(h->p, h->d, 0.0, 0, 1, -1, budget_of(h), terrain_of(h), weights_of(h), h->stream);
+    launch_decide(h->p, h->d, 0.0, 0, 1, -1, budget_of(h), terrain_of(h), weights_of(h), h->stream);
     h->slots_fresh = true;
 }
 
@@ -129,23 +130,23 @@ static void iteration_launches(hsddp_handle h, const std::vector<double> &trials
         // line-search trial, quirk A2) unless the cost parameters changed since (slots_fresh)
         Params pl = p;
         pl.lq_slots = h->slots_fresh ? 0 : 1;
-        launch_lq(pl, d, terrain_of(h), st);
+        launch_lq(pl, d, terrain_of(h), weights_of(h), st);
     }
     tm.end(0, e0);
     tm.begin(1, e0);
-    launch_riccati(p, d, st);
+    launch_riccati(p, d, weights_of(h), st);
     tm.end(1, e0);
     // the linear rollout with multiple shooting only (MultiPhaseDDP.cpp:326-329); with single
     // shooting the sweep forms dV and the merit (k_riccati's DV instantiation)
     if (!p.ms0) {
         tm.begin(4, e0);
-        launch_lin_rollout(p, d, st);
+        launch_lin_rollout(p, d, weights_of(h), st);
         tm.end(4, e0);
     }
     tm.begin(2, e0);
     for (size_t t = 0; t < trials.size(); ++t) {
-        launch_rollout(p, d, trials[t], t + 1 == trials.size(), 0, (int)t, budget_of(h), terrain_of(h), st);
-        launch_decide(p, d, trials[t], t + 1 == trials.size(), 0, (int)t, budget_of(h), terrain_of(h), st);
+        launch_rollout(p, d, trials[t], t + 1 == trials.size(), 0, (int)t, budget_of(h), terrain_of(h), weights_of(h), st);
+        launch_decide(p, d, trials[t], t + 1 == trials.size(), 0, (int)t, budget_of(h), terrain_of(h), weights_of(h), st);
     }
     tm.end(2, e0);
     h->slots_fresh = true;
@@ -172,7 +173,7 @@ static int graph_launch(hsddp_handle h, const std::vector<double> &trials, int p
     for (auto &c : h->iter_graph)
         if (c.exec && c.par == par && !std::memcmp(&c.p, &pl, sizeof(Params)) &&
             !std::memcmp(&c.d, &h->d, sizeof(Bufs)) && c.alpha == h->opt.alpha && c.budget == budget_of(h) &&
-            c.terrain == terrain_of(h))
+            c.terrain == terrain_of(h) && c.weights == weights_of(h))
             hit = &c;
     if (!hit) {
         auto &g = h->iter_graph[h->iter_graph_next];
@@ -204,6 +205,7 @@ static int graph_launch(hsddp_handle h, const std::vector<double> &trials, int p
         g.alpha = h->opt.alpha;
         g.budget = budget_of(h);
         g.terrain = terrain_of(h);  // (null: terrain off — other instantiations, other arguments)
+        g.weights = weights_of(h);  // (null: the table off)
         g.par = par;
         hit = &g;
     }

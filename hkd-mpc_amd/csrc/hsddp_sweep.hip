@@ -217,9 +217,12 @@ struct Phase {
 // Phase layout entries with a runtime phase index, read from the kernel-argument segment (scalar
 // loads): indexing the by-value Params directly makes the compiler copy it to scratch.
 
-template <typename real, typename ItemT>
-DEV void load_phase(const Params &p, const Bufs &d, ItemT &I, int b, int i, int pp, Phase<real> &ph)
+// wt: where the weights come from (TerrT: Params, or the row of the lane's element b)
+template <typename real, typename ItemT, typename WT>
+DEV void load_phase(const Params &p, const Bufs &d, ItemT &I, int b, int i, int pp, Phase<real> &ph, const WT &wt)
 {
+    const auto &ww = wt.w(p, b);
+    const auto &wk = wt.wk(b);  // (runtime field indices)
     const int *cs = d.contacts + ((size_t)b * (p.P + 1) + i) * 4;
     int c[4];
 #pragma unroll
@@ -234,23 +237,23 @@ DEV void load_phase(const Params &p, const Bufs &d, ItemT &I, int b, int i, int 
     }
     SSYNC();
     const int pos = pp & 15, cq = (ph.cmask >> ((pos / 3) & 3)) & 1;
-    ph.dtr = (real)(p.dt * (cq ? p.r_grf : p.r_qJd));
+    ph.dtr = (real)(p.dt * (cq ? ww.r_grf : ww.r_qJd));
     const int cz = (ph.cmask >> ((pp < HC ? pp : 0) / 3)) & 1;
-    ph.dtrz = (real)(p.dt * (cz ? p.r_qJd : p.r_grf));
+    ph.dtrz = (real)(p.dt * (cz ? ww.r_qJd : ww.r_grf));
     // lxx row pp (HKDCost.cpp:32: dt Q + dt D^T Qfoot D)
     const int r = pp < NX ? pp : 0;
-    double dg = p.dt * (r < 12 ? kparams()->qbase[r] : p.q_qJ * (1 - ((ph.cmask >> ((r - 12) / 3)) & 1)));
+    double dg = p.dt * (r < 12 ? wk.qbase[r] : ww.q_qJ * (1 - ((ph.cmask >> ((r - 12) / 3)) & 1)));
     ph.xmask = 0;
     ph.xw = 0;
     if (r >= 3 && r < 6) {
-        const double fw = p.dt * (p.foot_gain * kparams()->foot_w[r - 3]);
+        const double fw = p.dt * (ww.foot_gain * wk.foot_w[r - 3]);
 #pragma unroll
         for (int l = 0; l < 4; ++l) dg += c[l] ? fw : 0.0;
         ph.xmask = ph.cmask;
         ph.xw = (real)fw;
     } else if (r >= 12) {
         const int m = r - 12;
-        const double w = ((ph.cmask >> (m / 3)) & 1) ? p.dt * (p.foot_gain * kparams()->foot_w[m % 3]) : 0.0;
+        const double w = ((ph.cmask >> (m / 3)) & 1) ? p.dt * (ww.foot_gain * wk.foot_w[m % 3]) : 0.0;
         dg += w;
         ph.xmask = 1;
         ph.xw = (real)w;
@@ -873,9 +876,10 @@ __device__ __attribute__((noinline)) void phase_knots_masked(unsigned lds, int f
 // sum over every knot of Qu^T dU (= dV_1 = -dV_2 of the sweep, SinglePhase.cpp:359-362,
 // MultiPhaseDDP.cpp:224-226), on every lane of the half.  masks (wave-uniform; the one-wave sweep
 // only): phases may take the loops specialised on their contact mask (sweep_masks).
-template <typename real, bool EL, bool DV, int CSW = -1, int WPE = 2, typename LdsT = Lds<real>>
+// wt: the weights' source (load_phase).
+template <typename real, bool EL, bool DV, int CSW = -1, int WPE = 2, typename LdsT = Lds<real>, typename WT = TerrT<false>>
 DEV int sweep_pair(const Params &p, const Bufs &d, LdsT &S, const Lane &L, const Item<real> &it, double &dv,
-                   bool masks = false)
+                   bool masks = false, const WT &wt = WT{nullptr, nullptr})
 {
     constexpr bool CS = CSW >= 0;  // wave CSW of the column split (k_riccati_cs)
     int ib = 0, par = 0;           // (CS) image buffer, M / Z image roles
@@ -895,7 +899,7 @@ DEV int sweep_pair(const Params &p, const Bufs &d, LdsT &S, const Lane &L, const
     const int P = PL.P();
     for (int i = P - 1; i >= 0; --i) {
         Phase<real> ph;
-        load_phase<real>(p, d, S.it[L.e], b, i, pp, ph);
+        load_phase<real>(p, d, S.it[L.e], b, i, pp, ph, wt);
         const double *rec = d.term + ((size_t)b * p.P + i) * TW;
         if (i == P - 1) {
 #pragma unroll
@@ -1136,9 +1140,12 @@ using namespace sweep;
 // the sweep with each element's mu, then (for an element whose first sweep fails and that the
 // parallel retry cannot take) mu = max(mu * update_regularization, 1e-3) until a sweep succeeds or
 // mu > 1e2, then mu / 20 (0 below 1e-6) as the next regularisation.
-template <typename real, bool EL, bool DV, int WPB>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB == 2 ? SWEEP_WPB2_WPE : 2))) void k_riccati(Params p, Bufs d, int masks)
+// wp: the weight table (hsddp_set_element_weights), or nothing: Params' weights, today's arguments
+// and code (TerrT, hsddp_device.h)
+template <typename real, bool EL, bool DV, int WPB, typename... WP>
+__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB == 2 ? SWEEP_WPB2_WPE : 2))) void k_riccati(Params p, Bufs d, int masks, WP... wp)
 {
+    const auto wt = terrain_of(wp...);
     // WPB independent waves per workgroup, each with its own LDS and element pair (no barrier couples
     // them; sweep_wpb)
     __shared__ Lds<real> SS[WPB];
@@ -1177,7 +1184,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB ==
         it.act = need;
         it.reg = (real)reg;
         double dv;
-        const int fk = sweep_pair<real, EL, DV, -1, (WPB == 2 ? SWEEP_WPB2_WPE : 2)>(p, d, S, L, it, dv, masks != 0);
+        const int fk = sweep_pair<real, EL, DV, -1, (WPB == 2 ? SWEEP_WPB2_WPE : 2)>(p, d, S, L, it, dv, masks != 0, wt);
         if (need) {
             if (fk < 0) {
                 ok = true;
@@ -1221,7 +1228,6 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB ==
         if (DV && ok) merit_step(p, E, dvk, -dvk);
     }
 }
-
 // k_riccati for small batches (column split, launch_riccati's choice): one element pair per
 // workgroup of two waves, wave W running sweep_pair with knot<W> — the same sweeps, attempts and
 // outcomes as k_riccati (each wave computes the values the other multiplies by, so both take the
@@ -1230,8 +1236,8 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(WPB ==
 // and its knot is one dependent chain of ~11 k cycles; split, each wave issues ~970 of the 1 197
 // VALU instructions of a knot (static count of the knot loops) and the knot takes ~10 % less
 // (sweep_split).
-template <bool EL, bool DV, int W>
-DEV void riccati_cs_wave(const Params &p, const Bufs &d, LdsCS<double> &S)
+template <bool EL, bool DV, int W, typename WT>
+DEV void riccati_cs_wave(const Params &p, const Bufs &d, LdsCS<double> &S, const WT &wt)
 {
     using real = double;
     const Lane L = make_lane();
@@ -1259,7 +1265,7 @@ DEV void riccati_cs_wave(const Params &p, const Bufs &d, LdsCS<double> &S)
         it.act = need;
         it.reg = (real)reg;
         double dv;
-        const int fk = sweep_pair<real, EL, DV, W>(p, d, S, L, it, dv);
+        const int fk = sweep_pair<real, EL, DV, W>(p, d, S, L, it, dv, false, wt);
         if (attempt == 0 && p.retry_cap > 0) {  // wave 0 takes the retry slots, both read them
             if (W == 0 && need && fk >= 0 && L.pp == 0) {
                 const int f = atomicAdd(d.retry_count, 1);
@@ -1297,23 +1303,23 @@ DEV void riccati_cs_wave(const Params &p, const Bufs &d, LdsCS<double> &S)
     }
 }
 
-template <bool EL, bool DV>
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k_riccati_cs(Params p, Bufs d)
+template <bool EL, bool DV, typename... WP>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k_riccati_cs(Params p, Bufs d, WP... wp)
 {
     __shared__ LdsCS<double> S;
     zero_init(S, threadIdx.x & 63);
     __syncthreads();
-    if (threadIdx.x < 64) riccati_cs_wave<EL, DV, 0>(p, d, S);
-    else riccati_cs_wave<EL, DV, 1>(p, d, S);
+    if (threadIdx.x < 64) riccati_cs_wave<EL, DV, 0>(p, d, S, terrain_of(wp...));
+    else riccati_cs_wave<EL, DV, 1>(p, d, S, terrain_of(wp...));
 }
-
 // The retries of backward_sweep_regularized for the elements k_riccati deferred, all at once:
 // item (f, a) sweeps deferred element f with the a-th next mu of the schedule into its own scratch
 // rows, two items per wave.  Every attempt is the sweep the sequential loop would run with that mu,
 // so taking the first success (k_riccati_select) gives the loop's result.
-template <typename real, bool EL, bool DV>
-__global__ __launch_bounds__(64, 2) void k_riccati_retry(Params p, Bufs d, int masks)
+template <typename real, bool EL, bool DV, typename... WP>
+__global__ __launch_bounds__(64, 2) void k_riccati_retry(Params p, Bufs d, int masks, WP... wp)
 {
+    const auto wt = terrain_of(wp...);
     __shared__ Lds<real> S;
     const Lane L = make_lane();
     zero_init(S, L.lane);
@@ -1343,11 +1349,10 @@ __global__ __launch_bounds__(64, 2) void k_riccati_retry(Params p, Bufs d, int m
     it.K = (Global<real>)((real *)d.retry_K + slot * p.Kc * KCW);
     it.dU = (Global<double>)(d.retry_dU + slot * p.Kc * NX);
     double dv;
-    const int fk = sweep_pair<real, EL, DV>(p, d, S, L, it, dv, masks != 0);
+    const int fk = sweep_pair<real, EL, DV>(p, d, S, L, it, dv, masks != 0, wt);
     if (act && L.pp == 0) *flag = fk < 0 ? 1 : -1 - fk;  // success, or -1 - (the failing control slot)
     if (DV && act && L.pp == 0) d.retry_dv[slot] = dv;
 }
-
 // The outcome of backward_sweep_regularized for each deferred element: the first attempt that
 // succeeded (its gains and dU rows copied to the element), mu / 20 (0 below 1e-6) as the next
 // regularisation; when none succeeds (mu passed 1e2: status 1, bad_solve) the element's rows are
@@ -1465,40 +1470,40 @@ static int sweep_wpb(const Params &p)
 
 // k_riccati for one precision and wave count per workgroup (axes that are not flags: fp32 has W = 1 only)
 template <typename real, int W>
-static void launch_sweep(const Params &p, const Bufs &d, dim3 gw, int masks, hipStream_t st)
+static void launch_sweep(const Params &p, const Bufs &d, const Wts *weights, dim3 gw, int masks, hipStream_t st)
 {
-    with_flags([&](auto el, auto dv) {
-        hipLaunchKernelGGL((k_riccati<real, decltype(el)::value, decltype(dv)::value, W>), gw, dim3(64 * W), 0, st, p, d, masks);
-    }, p.elem_layout, p.ms0);
+    with_flags_table([&](auto el, auto dv, auto... wp) {
+        hipLaunchKernelGGL((k_riccati<real, decltype(el)::value, decltype(dv)::value, W>), gw, dim3(64 * W), 0, st, p, d, masks, wp...);
+    }, weights, p.elem_layout, p.ms0);
 }
 // the parallel retries of the elements whose first sweep failed, then the first success of each
 template <typename real>
-static void launch_retry(const Params &p, const Bufs &d, int masks, hipStream_t st)
+static void launch_retry(const Params &p, const Bufs &d, const Wts *weights, int masks, hipStream_t st)
 {
     const dim3 gr((unsigned)(p.retry_cap * (p.retry_m + (p.retry_m & 1)) / 2)), gs((unsigned)p.retry_cap);
-    with_flags([&](auto el, auto dv) {
-        hipLaunchKernelGGL((k_riccati_retry<real, decltype(el)::value, decltype(dv)::value>), gr, dim3(64), 0, st, p, d, masks);
-    }, p.elem_layout, p.ms0);
+    with_flags_table([&](auto el, auto dv, auto... wp) {
+        hipLaunchKernelGGL((k_riccati_retry<real, decltype(el)::value, decltype(dv)::value>), gr, dim3(64), 0, st, p, d, masks, wp...);
+    }, weights, p.elem_layout, p.ms0);
     hipLaunchKernelGGL(k_riccati_select<real>, gs, dim3(64), 0, st, p, d);
 }
 
-void launch_riccati(const Params &p, const Bufs &d, hipStream_t st)
+void launch_riccati(const Params &p, const Bufs &d, const Wts *weights, hipStream_t st)
 {
     // (the retry list count is zeroed by the k_lq launch just before, in its first terminal task)
     const dim3 g1((unsigned)(p.elem_layout ? p.n_pairs : (p.B + 1) / 2));
     // instantiations: precision x layout mode x single shooting (DV)
     const int wpb = sweep_wpb(p), masks = sweep_masks();
     const dim3 gw((unsigned)(((p.elem_layout ? p.n_pairs : (p.B + 1) / 2) + wpb - 1) / wpb));
-    if (p.fp32) launch_sweep<float, 1>(p, d, gw, masks, st);
+    if (p.fp32) launch_sweep<float, 1>(p, d, weights, gw, masks, st);
     else if (sweep_split(p))
-        with_flags([&](auto el, auto dv) {
-            hipLaunchKernelGGL((k_riccati_cs<decltype(el)::value, decltype(dv)::value>), g1, dim3(128), 0, st, p, d);
-        }, p.elem_layout, p.ms0);
-    else if (wpb == 2) launch_sweep<double, 2>(p, d, gw, masks, st);
-    else launch_sweep<double, 1>(p, d, gw, masks, st);
+        with_flags_table([&](auto el, auto dv, auto... wp) {
+            hipLaunchKernelGGL((k_riccati_cs<decltype(el)::value, decltype(dv)::value>), g1, dim3(128), 0, st, p, d, wp...);
+        }, weights, p.elem_layout, p.ms0);
+    else if (wpb == 2) launch_sweep<double, 2>(p, d, weights, gw, masks, st);
+    else launch_sweep<double, 1>(p, d, weights, gw, masks, st);
     if (p.retry_cap > 0) {
-        if (p.fp32) launch_retry<float>(p, d, masks, st);
-        else launch_retry<double>(p, d, masks, st);
+        if (p.fp32) launch_retry<float>(p, d, weights, masks, st);
+        else launch_retry<double>(p, d, weights, masks, st);
     }
 }
 

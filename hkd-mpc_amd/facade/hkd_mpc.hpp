@@ -182,6 +182,20 @@ public:
         chk(hsddp_set_terrain(h, m.data(), g.data()));
     }
 
+    // Per-robot cost weights (hsddp_set_element_weights): the robot's HKD weights from the next solve
+    // on, where the settings give one set for the batch.  The row belongs to the robot: it stays
+    // through every tick and through restart().  Call between ticks.
+    void set_weights(int robot, const hsddp_hkd_weights &w)
+    {
+        if (robot < 0 || robot >= B) throw std::runtime_error("set_weights: no such robot");
+        wait();
+        std::lock_guard<std::mutex> lk(mpc_mutex);
+        std::vector<hsddp_hkd_weights> rows((size_t)B, w);
+        std::vector<int> mask((size_t)B, 0);
+        mask[(size_t)robot] = 1;
+        chk(hsddp_set_element_weights(h, rows.data(), mask.data()));
+    }
+
     // HKDMPCSolver::mpcdata_lcm_handler (HKDMPC.cpp:166-200): msgs[B]
     void mpcdata_lcm_handler(const std::vector<hkd_data_lcmt> &msgs)
     {

@@ -330,6 +330,53 @@ class Solver:
         check(lib().hsddp_get_terrain(self._h, dp(out["mu"]), dp(out["ground"])))
         return out
 
+    def set_element_weights(self, weights, mask=None) -> None:
+        """Per-robot cost weights (hsddp_set_element_weights): weights is a sequence of B hsddp.Weights
+        a ctypes array (hsddp.Weights * B), or a float64 array [B][46] of the rows' fields in the
+        structure's order (both passed on as they stand, no per-robot copy); robot b with mask[b] != 0 (mask None: every robot) takes
+        weights[b], the others keep theirs.  The first call turns the table on, robots never set read
+        the handle's weights; None turns it off again.  The rows belong to the robot: shift, advance
+        and restart_elements leave them alone, copy / export / import carry them.  Call between
+        ticks."""
+        if weights is None:
+            check(lib().hsddp_set_element_weights(self._h, None, None))
+            return
+        if len(weights) != self.B:
+            raise HSDDPError(f"weights: {len(weights)} rows, expected {self.B}")
+        nf = C.sizeof(Weights) // 8
+        if isinstance(weights, np.ndarray):
+            rows = np.ascontiguousarray(weights, dtype=np.float64)
+            if rows.shape != (self.B, nf):
+                raise HSDDPError(f"weights: shape {rows.shape}, expected ({self.B}, {nf})")
+            addr = rows.ctypes.data
+        elif isinstance(weights, C.Array) and weights._type_ is Weights:
+            rows, addr = weights, C.addressof(weights)
+        else:
+            rows = (Weights * self.B)()
+            for b in range(self.B):
+                if not isinstance(weights[b], Weights):
+                    raise HSDDPError(f"weights[{b}]: not an hsddp.Weights")
+                C.memmove(C.byref(rows, b * C.sizeof(Weights)), C.byref(weights[b]), C.sizeof(Weights))
+            addr = C.addressof(rows)
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, dtype=np.int32)
+            if m.shape != (self.B,):
+                raise HSDDPError(f"mask: shape {m.shape}, expected ({self.B},)")
+        check(lib().hsddp_set_element_weights(self._h, addr, None if m is None else m.ctypes.data))
+
+    def element_weights(self) -> list:
+        """The B robots' hsddp.Weights (hsddp_get_element_weights): the handle's weights for every robot
+        while the table is off."""
+        rows = (Weights * self.B)()
+        check(lib().hsddp_get_element_weights(self._h, C.addressof(rows)))
+        out = []
+        for b in range(self.B):
+            w = Weights()
+            C.memmove(C.byref(w), C.byref(rows, b * C.sizeof(Weights)), C.sizeof(Weights))
+            out.append(w)
+        return out
+
     def set_value_export(self, on: bool = True) -> None:
         """Store G[0], H[0] of every phase in each sweep (SinglePhase::get_value_approx)."""
         check(lib().hsddp_set_value_export(self._h, int(bool(on))))

@@ -128,6 +128,7 @@ EXPORTS = [
     "hsddp_restart_elements", "hsddp_set_element_budgets", "hsddp_get_strides",
     "hsddp_copy_elements", "hsddp_element_record_bytes", "hsddp_export_elements", "hsddp_import_elements",
     "hsddp_set_terrain", "hsddp_get_terrain",
+    "hsddp_set_element_weights", "hsddp_get_element_weights",
 ]
 
 
@@ -231,6 +232,9 @@ def lib():
     if hasattr(L, "hsddp_set_terrain"):  # (older A/B builds lack the per-phase terrain)
         L.hsddp_set_terrain.argtypes = [V, DP, DP]
         L.hsddp_get_terrain.argtypes = [V, DP, DP]
+    if hasattr(L, "hsddp_set_element_weights"):  # (older A/B builds lack the per-robot weights)
+        L.hsddp_set_element_weights.argtypes = [V, C.c_void_p, C.c_void_p]
+        L.hsddp_get_element_weights.argtypes = [V, C.c_void_p]
     _lib = L
     return L
 

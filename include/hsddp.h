@@ -266,6 +266,33 @@ int hsddp_set_terrain(hsddp_handle h, const double *mu, const double *ground);
 /* The terrain rows [B][P] (either pointer may be NULL): the cparams values for rows past an
  * element's phases, and for every row while terrain is off. */
 int hsddp_get_terrain(hsddp_handle h, double *mu, double *ground);
+/* Per-robot cost weights: one hsddp_hkd_weights row per element where desc->weights gives one set
+ * for the handle.  In the reference the weights are members of the cost objects of one HKDProblem
+ * (HKDCost.h:14-36, 56-69; HKDCost.cpp:49,63): one problem has one set, so a batch of problems has
+ * one set per problem.
+ * w [B], mask [B] or NULL for every element: element b with mask[b] != 0 takes w[b], the others keep
+ * what they have.  The first call turns the table on; elements never set read desc->weights.
+ * w = NULL turns the table off again: every element back at desc->weights, and the handle runs the
+ * kernels, arguments and graphs of a handle that never called this.  Negative weights are legal,
+ * as they are in desc->weights.
+ * HSDDP_ERR_ARG (the handle unchanged): a NULL handle, no problem uploaded, a non-finite field in
+ * a row whose mask is set (other rows are not read).
+ * A call that changes a row makes the next iteration's LQ pass recompute the slot costs (they
+ * belong to the old weights), as the other cost-parameter changes do; the warm start, the
+ * constraint parameters and the stored constraint values stay.
+ * The rows belong to the robot, not to a phase: hsddp_shift, hsddp_shift_elements and
+ * hsddp_advance leave them alone, and hsddp_restart_elements keeps a restarted robot's row — the
+ * same robot and tuning with a new problem.  (Terrain differs: its rows belong to the constraint
+ * objects a restart replaces, so a restart returns them to cparams.)  hsddp_copy_elements,
+ * hsddp_export_elements and hsddp_import_elements carry the row with the robot: an arriving robot
+ * with a row turns the destination's table on (its residents reading the destination's
+ * desc->weights); a robot from a handle with the table off takes the handle's weights as its row
+ * where the destination's table is on.  The two handles' desc->weights must still be equal.
+ * hsddp_download_lq rebuilds lxx and luu from the robot's row.  Call between ticks. */
+int hsddp_set_element_weights(hsddp_handle h, const hsddp_hkd_weights *w, const int *mask);
+/* The weight rows [B]: with the table off, desc->weights B times.  HSDDP_ERR_ARG: a NULL handle or
+ * output, no problem uploaded. */
+int hsddp_get_element_weights(hsddp_handle h, hsddp_hkd_weights *w);
 
 /* MultiPhaseDDP::solve (MultiPhaseDDP.cpp:232-428) for every element.  With early exits on, each
  * inner iteration is replayed from a cached hipGraph and stats carries ms_total but no per-phase

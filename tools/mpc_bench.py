@@ -71,9 +71,12 @@ def main():
     ap.add_argument("--terrain", action="store_true",
                     help="per-phase terrain (set_terrain): a random friction coefficient in [0.3, 0.9] per robot and a "
                          "ground height within +-0.03 per phase, the whole table set again every tick after the advance")
+    ap.add_argument("--weights", action="store_true",
+                    help="per-robot cost weights (set_element_weights): every field of each robot's row drawn within "
+                         "+-30 %% of the defaults, the whole table set again every tick after the advance")
     args = ap.parse_args()
-    if args.host_state + args.measured + args.closed_loop + (args.restart_frac is not None) + args.terrain > 1:
-        ap.error("--host-state, --measured, --closed-loop, --restart-frac and --terrain are separate legs")
+    if args.host_state + args.measured + args.closed_loop + (args.restart_frac is not None) + args.terrain + args.weights > 1:
+        ap.error("--host-state, --measured, --closed-loop, --restart-frac, --terrain and --weights are separate legs")
     B = args.batch
     tab, dt = hsddp.load_quad_reference(os.path.join(ROOT, "tests", "golden", "ref_trot.csv"))
     rng = np.random.default_rng(7)
@@ -91,6 +94,16 @@ def main():
     if args.terrain:
         rng_t = np.random.default_rng(13)
         s.set_terrain(np.repeat(rng_t.uniform(0.3, 0.9, (B, 1)), s.P, axis=1), rng_t.uniform(-0.03, 0.03, (B, s.P)))
+    t_weights, rows = [], None
+    if args.weights:
+        import ctypes
+        rng_w = np.random.default_rng(17)
+        base = hsddp.Weights()
+        hsddp.lib().hsddp_default_weights(ctypes.byref(base))
+        n = ctypes.sizeof(hsddp.Weights) // 8
+        vals = np.frombuffer(ctypes.string_at(ctypes.addressof(base), 8 * n), np.float64) * rng_w.uniform(0.7, 1.3, (B, n))
+        rows = np.ascontiguousarray(vals)  # [B][46]: passed on as it stands
+        s.set_element_weights(rows)
     n_restart = 0
     if restarts and args.restart_frac > 0:
         n_restart = min(B, max(1, int(round(args.restart_frac * B))))
@@ -145,6 +158,15 @@ def main():
             t = s.terrain()  # the rows the phases carried on; a phase that entered took the last one's
             s.set_terrain(t["mu"], t["ground"])
             t_terrain.append(time.perf_counter() - tt)
+            s.update_problem(None, xt)
+        elif args.weights:  # advance -> set_element_weights -> x0 -> solve (the rows go up with the solve's first launch)
+            xt = x0 + rng.uniform(-.01, .01, x0.shape)
+            t0 = time.perf_counter()
+            flags += sum(s.advance(None, 1))
+            tw = time.perf_counter()
+            rows[it % B, 12] *= 1.0 + 1e-9  # (q_qJ of one robot: an unchanged table is not uploaded again)
+            s.set_element_weights(rows)
+            t_weights.append(time.perf_counter() - tw)
             s.update_problem(None, xt)
         else:
             xt = x0 + rng.uniform(-.01, .01, x0.shape)
@@ -203,6 +225,10 @@ def main():
             s.warm_start()
             t_up.append(time.perf_counter() - tu)
         out["ms_per_tick_median"]["reupload_all"] = med(t_up)
+    if args.weights:
+        out["metric"] = "MPC tick with per-robot weights (advance + set_element_weights + x0 + solve + extract), HKD trot reference file"
+        out["ms_per_tick_median"]["advance"] = med(np.array(t_adv) - np.array(t_weights))
+        out["ms_per_tick_median"]["weights"] = med(t_weights)
     if args.terrain:
         out["metric"] = "MPC tick with per-phase terrain (advance + set_terrain + x0 + solve + extract), HKD trot reference file"
         out["ms_per_tick_median"]["advance"] = med(np.array(t_adv) - np.array(t_terrain))
