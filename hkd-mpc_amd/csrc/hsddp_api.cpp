@@ -236,6 +236,8 @@ extern "C" int hsddp_destroy(hsddp_handle h)
     if (h->terrain_up) hipEventDestroy(h->terrain_up);
     if (h->weights_pin) hipHostFree(h->weights_pin);
     if (h->weights_up) hipEventDestroy(h->weights_up);
+    if (h->pw_pin) hipHostFree(h->pw_pin);
+    if (h->pw_up) hipEventDestroy(h->pw_up);
     if (h->copy_stream) hipStreamSynchronize(h->copy_stream);
     for (int q = 0; q < 2; ++q) {
         if (h->cmd_dev[q]) hipFree(h->cmd_dev[q]);
@@ -404,6 +406,7 @@ extern "C" int hsddp_set_element_layouts(hsddp_handle h, const int *n_phases, co
     if ((rc = set_layouts(h, lays))) return rc;
     h->reach_el.assign((size_t)B * HSDDP_MAX_PHASES, 0);  // HKDProblem.cpp:56-57 (quirk A15)
     h->terrain.clear();       // (the phases it described are gone)
+    drop_phase_weights(h);    // (and the cost objects the overrides belonged to)
     h->have_problem = false;  // inputs of the new layouts next (hsddp_upload_problem)
     h->sim_fresh = false;
     h->contacts_current = false;
@@ -469,6 +472,7 @@ extern "C" int hsddp_set_layout(hsddp_handle h, int n_phases, const int *horizon
     for (int i = 0; i < n_phases; ++i) reach[i] = reach_end && reach_end[i] ? 1 : 0;
     adopt_shared_layout(h, L, reach);
     h->terrain.clear();       // (the phases it described are gone)
+    drop_phase_weights(h);    // (and the cost objects the overrides belonged to)
     h->have_problem = false;  // inputs of the new layout next (hsddp_upload_problem)
     h->sim_fresh = false;
     h->need_inputs = false;
@@ -738,7 +742,7 @@ extern "C" int hsddp_simulate_policy(hsddp_handle h, int n_samples, int n_steps,
         HIPCHK(hipEventCreate(&ev[1]));
         HIPCHK(hipEventRecord(ev[0], h->stream));
     }
-    if ((rc = sync_terrain(h)) || (rc = sync_weights(h))) return rc;
+    if ((rc = sync_terrain(h)) || (rc = sync_weights(h)) || (rc = sync_phase_weights(h))) return rc;
     launch_simulate_policy(p, h->d, a, terrain_of(h), weights_of(h), h->stream);
     HIPCHK(hipGetLastError());
     if (timing) {
@@ -1047,6 +1051,7 @@ extern "C" int hsddp_set_element_weights(hsddp_handle h, const hsddp_hkd_weights
     if (!w) {  // the table off: every robot back at the handle's weights
         if (h->weights.empty()) return HSDDP_OK;
         h->weights.clear();
+        h->pw_stale = true;
         h->slots_fresh = false;
         return HSDDP_OK;
     }
@@ -1063,6 +1068,7 @@ extern "C" int hsddp_set_element_weights(hsddp_handle h, const hsddp_hkd_weights
     }
     if (changed) {
         h->weights_stale = true;
+        h->pw_stale = true;      // (the phases without an override read the robot's row)
         h->slots_fresh = false;  // the stored slot costs were formed with the old weights
     }
     return HSDDP_OK;
@@ -1118,6 +1124,127 @@ int hsddp::sync_weights(hsddp_handle h)
         std::fprintf(stderr, "weights upload ms: %.4f (%zu bytes)\n", ms, bytes);
     }
     h->weights_stale = false;
+    return HSDDP_OK;
+}
+
+// ---- per-phase weights -----------------------------------------------------------------------------
+// The host flags and rows are the source of truth (hsddp_handle.h); the kernels' dense table of
+// effective rows follows by sync_phase_weights.
+extern "C" int hsddp_set_phase_weights(hsddp_handle h, const hsddp_hkd_weights *w, const int *mask)
+{
+    if (!h) return fail(HSDDP_ERR_ARG, "null handle");
+    if (!h->have_problem) return fail(HSDDP_ERR_ARG, "upload the problem first");
+    const size_t B = h->p.B, P = h->p.P;
+    if (!w) {  // every override gone: the handle as one that never called this
+        drop_phase_weights(h);
+        return HSDDP_OK;
+    }
+    bool any = false;
+    for (size_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < (size_t)layout_of(h, b).P; ++i) {
+            if (mask && !mask[b * P + i]) continue;
+            any = true;
+            if (!weights_finite(w[b * P + i])) return fail(HSDDP_ERR_ARG, "phase weights: a value is not finite");
+        }
+    if (!any) return HSDDP_OK;
+    if (int rc = ensure_phase_weights_table(h)) return rc;
+    bool changed = false;
+    if (h->pw_set.empty()) {
+        h->pw_set.assign(B * P, 0);
+        h->pw.assign(B * P * NW, 0.0);
+    }
+    for (size_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < (size_t)layout_of(h, b).P; ++i) {
+            const size_t q = b * P + i;
+            if (mask && !mask[q]) continue;
+            if (!h->pw_set[q] || std::memcmp(&h->pw[q * NW], &w[q], sizeof w[q])) changed = true;
+            h->pw_set[q] = 1;
+            std::memcpy(&h->pw[q * NW], &w[q], sizeof w[q]);
+        }
+    if (changed) {
+        h->pw_stale = true;
+        h->slots_fresh = false;  // the stored slot costs were formed with the old weights
+    }
+    return HSDDP_OK;
+}
+
+extern "C" int hsddp_get_phase_weights(hsddp_handle h, hsddp_hkd_weights *w, int *is_set)
+{
+    if (!h) return fail(HSDDP_ERR_ARG, "null handle");
+    if (!h->have_problem) return fail(HSDDP_ERR_ARG, "upload the problem first");
+    if (!w) return fail(HSDDP_ERR_ARG, "null output");
+    const size_t B = h->p.B, P = h->p.P;
+    for (size_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < P; ++i) {
+            w[b * P + i] = weights_of(h, b, (int)i);
+            if (is_set) is_set[b * P + i] = h->pw_set.empty() ? 0 : h->pw_set[b * P + i];
+        }
+    return HSDDP_OK;
+}
+
+int hsddp::ensure_phase_weights_table(hsddp_handle h)
+{
+    if (h->pw_dev) return HSDDP_OK;
+    HIPCHK(hipSetDevice(h->desc.device));
+    // at the largest phase stride, so no layout change moves it; piece by piece, as ensure_weights_table
+    const size_t cap = (size_t)h->p.B * HSDDP_MAX_PHASES;
+    if (!h->pw_pin) HIPCHK(hipHostMalloc((void **)&h->pw_pin, cap * sizeof(PWts), 0));
+    if (!h->pw_up) {
+        HIPCHK(hipEventCreateWithFlags(&h->pw_up, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(h->pw_up, h->stream));
+    }
+    return dalloc(h, h->pw_dev, cap);
+}
+
+void hsddp::adopt_phase_weights(hsddp_handle h, std::vector<int> &set, std::vector<double> &rows)
+{
+    h->pw_set.swap(set);
+    h->pw.swap(rows);
+    settle_phase_weights(h);
+}
+
+void hsddp::settle_phase_weights(hsddp_handle h)
+{
+    bool any = false;
+    for (int f : h->pw_set) any = any || f;
+    h->slots_fresh = false;
+    if (!any) {  // the last override left: the handle as one without
+        h->pw_set.clear();
+        h->pw.clear();
+        return;
+    }
+    h->pw_stale = true;
+}
+
+int hsddp::sync_phase_weights(hsddp_handle h)
+{
+    if (h->pw_set.empty() || !h->pw_stale) return HSDDP_OK;
+    if (!h->pw_dev) return fail(HSDDP_ERR_DEVICE, "phase weight rows without a device table");
+    const size_t B = h->p.B, P = h->p.P, bytes = B * P * sizeof(PWts);
+    HIPCHK(hipSetDevice(h->desc.device));
+    HIPCHK(hipEventSynchronize(h->pw_up));  // (the last upload has read the staging)
+    for (size_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < P; ++i) weights_row(weights_of(h, b, (int)i), h->pw_pin[b * P + i].row);
+    // HSDDP_WEIGHTS_TIMING=1: the upload's device time (HIP events) to stderr (a diagnostic)
+    static const bool timing = std::getenv("HSDDP_WEIGHTS_TIMING") != nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (timing) {
+        HIPCHK(hipEventCreate(&ev[0]));
+        HIPCHK(hipEventCreate(&ev[1]));
+        HIPCHK(hipEventRecord(ev[0], h->stream));
+    }
+    HIPCHK(hipMemcpyAsync(h->pw_dev, h->pw_pin, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(h->pw_up, h->stream));
+    if (timing) {
+        float ms = 0;
+        HIPCHK(hipEventRecord(ev[1], h->stream));
+        HIPCHK(hipEventSynchronize(ev[1]));
+        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        hipEventDestroy(ev[0]);
+        hipEventDestroy(ev[1]);
+        std::fprintf(stderr, "phase weights upload ms: %.4f (%zu bytes)\n", ms, bytes);
+    }
+    h->pw_stale = false;
     return HSDDP_OK;
 }
 
@@ -1297,9 +1424,9 @@ extern "C" int hsddp_download_lq(hsddp_handle h, double *A, double *Bm, double *
                         bb[(12 + 3 * lg + a) * NX + 12 + 3 * lg + a] = dt * (1.0 - c[lg]);
                     }
             }
-            // the robot's weights in the kernels' form (its row, or the handle's)
+            // the weights of the knot's phase in the kernels' form (its override, the robot's row, or the handle's)
             Wts wr;
-            weights_row(weights_of(h, b), wr);
+            weights_row(weights_of(h, b, i), wr);
             if (l) l[o] = cost[b * S + kc + i];
             if (lx) for (int j = 0; j < NX; ++j) lx[o * NX + j] = r[LQ_LX + j];
             if (lu) for (int j = 0; j < NX; ++j) lu[o * NX + j] = r[LQ_LU + j];

@@ -59,10 +59,15 @@ DEV bool touchdown(const int *c, const int *cn, int l) { return c[l] == 0 && cn[
 // its weights once (`const auto &w = terr.w(p, b); ... w.r_grf ...`) and keeps its form.  wk(b)
 // is the same for runtime field indices: the kernel-argument segment (kparams) or the row — a
 // pointer to global memory, which a runtime index never copies to scratch.
-template <bool ON, bool WON = false>
+// Third mode (WM == 2, hsddp_set_phase_weights): the table holds one effective row per (element,
+// phase) at the phase stride, [B][P], and w(p, b, i) / wk(b, i) are the row of element b's phase i;
+// the plain and per-robot modes ignore i.  Every site passes the phase whose cost objects supply its
+// term in the reference: a knot's own phase, a terminal slot's phase.
+template <bool ON, int WM = 0>
 struct TerrT {
     const double *t;
     const Wts *wt;
+    static constexpr bool WON = WM != 0;
     static constexpr bool weights = WON;
     DEV double mu(const Params &p, int b, int i) const
     {
@@ -74,21 +79,25 @@ struct TerrT {
         if constexpr (ON) return t[((size_t)b * p.P + i) * 2 + 1];
         else return p.ground;
     }
-    DEV const std::conditional_t<WON, Wts, Params> &w(const Params &p, size_t b) const
+    DEV const std::conditional_t<WON, Wts, Params> &w(const Params &p, size_t b, int i) const
     {
-        if constexpr (WON) return wt[b];
+        if constexpr (WM == 2) return wt[b * p.P + i];
+        else if constexpr (WON) return wt[b];
         else return p;
     }
-    DEV std::conditional_t<WON, const Wts, KParams> &wk(size_t b) const
+    DEV std::conditional_t<WON, const Wts, KParams> &wk(size_t b, int i) const
     {
-        if constexpr (WON) return wt[b];
+        if constexpr (WM == 2) return wt[b * kparams()->P + i];
+        else if constexpr (WON) return wt[b];
         else return *kparams();
     }
 };
 DEV TerrT<false> terrain_of() { return {nullptr, nullptr}; }
 DEV TerrT<true> terrain_of(const double *t) { return {t, nullptr}; }
-DEV TerrT<false, true> terrain_of(const Wts *w) { return {nullptr, w}; }
-DEV TerrT<true, true> terrain_of(const double *t, const Wts *w) { return {t, w}; }
+DEV TerrT<false, 1> terrain_of(const Wts *w) { return {nullptr, w}; }
+DEV TerrT<true, 1> terrain_of(const double *t, const Wts *w) { return {t, w}; }
+DEV TerrT<false, 2> terrain_of(const PWts *w) { return {nullptr, &w->row}; }
+DEV TerrT<true, 2> terrain_of(const double *t, const PWts *w) { return {t, &w->row}; }
 
 // ---- the phase layout of element b ----------------------------------------------------------
 // The handle's layout (Params, read in place: runtime phase indices never index the by-value copy)

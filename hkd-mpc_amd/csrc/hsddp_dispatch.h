@@ -44,6 +44,21 @@ void with_flags_tables(F &&f, const T *table, const W *second, Flags... flags)
     else with_flags_table(f, table, flags...);
 }
 
+// ... and with the weights a handle reads (a WtsTab, hsddp_internal.h: `phase` while a phase has an
+// override, else `robot` while the per-robot table is on, else neither) as that last table
+template <typename F, typename WT, typename... Flags>
+auto with_flags_table(F &&f, WT w, Flags... flags) -> decltype((void)w.phase)
+{
+    if (w.phase) with_flags_table(f, w.phase, flags...);
+    else with_flags_table(f, w.robot, flags...);
+}
+template <typename F, typename T, typename WT, typename... Flags>
+auto with_flags_tables(F &&f, const T *table, WT w, Flags... flags) -> decltype((void)w.phase)
+{
+    if (w.phase) with_flags_tables(f, table, w.phase, flags...);
+    else with_flags_tables(f, table, w.robot, flags...);
+}
+
 static inline unsigned blocks_for(long n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 }  // namespace hsddp

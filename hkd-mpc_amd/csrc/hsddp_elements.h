@@ -12,8 +12,10 @@ namespace hsddp {
 // One fixed-size record per element: the header (the version word, the compatibility key and the
 // host bookkeeping), then the device rows packed at the capacity strides (S_cap state slots,
 // HSDDP_MAX_PHASES phases), every piece 16-byte aligned, the gain rows on a 128-byte line and the
-// record a whole number of lines.
-constexpr uint32_t RECORD_VERSION = 0x48454c33;  // "HEL3" (HEL1: no terrain rows in the header; HEL2: no weight row)
+// record a whole number of lines.  Since "HEL4" the element's phase overrides (PhaseOverrides,
+// hsddp_phases.h) sit in a block of whole lines between the header and the payload: the header
+// keeps its size and every payload piece its distance from the record's end.
+constexpr uint32_t RECORD_VERSION = 0x48454c34;  // "HEL4" (HEL1: no terrain rows; HEL2: no weight row; HEL3: no phase overrides)
 constexpr int REC_HIST = 256;  // solver-info history entries a record holds
 
 // What two handles must agree on for an element of one to continue in the other.
@@ -37,8 +39,11 @@ struct RecordHeader {
 };
 
 // byte offsets of a record's pieces from the record's start
+constexpr size_t PW_BLOCK = (sizeof(PhaseOverrides) + 127) & ~(size_t)127;
+
 struct RecordLayout {
     size_t bytes;
+    size_t pw;                           // the PhaseOverrides block (0: a layout without it)
     size_t K;                            // [Kc][KCW] reals
     size_t Xn, Xw, Dw, dX, rx, ru;       // [S_cap][24] doubles: nominal, working, Defect, dX, ref_x, ref_u
     size_t rf, d32;                      // [S_cap][12] doubles (ref_foot), [S_cap][24] floats (fp32 Defect)
@@ -49,10 +54,13 @@ struct RecordLayout {
     size_t con, x0, el, sel, hist;       // [(MAXP + 1) * 4] ints, [24], ElemState, int, [REC_HIST][4] floats
 };
 
-inline RecordLayout record_layout(int Kc, size_t S_cap, int fp32)
+// overrides: with the PhaseOverrides block, as every record the library writes or reads has it;
+// without: the header and the payload alone, the offsets the block then shifts by PW_BLOCK
+inline RecordLayout record_layout(int Kc, size_t S_cap, int fp32, bool overrides = false)
 {
     RecordLayout R{};
     size_t at = (sizeof(RecordHeader) + 127) & ~(size_t)127;
+    if (overrides) { R.pw = at; at += PW_BLOCK; }
     auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
     R.K = take((size_t)Kc * KCW * (fp32 ? 4 : 8));
     const size_t row = NX * sizeof(double);

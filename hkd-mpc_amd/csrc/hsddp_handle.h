@@ -52,6 +52,7 @@ struct hsddp_handle_t {
         const int *budget = nullptr;
         const double *terrain = nullptr;
         const hsddp::Wts *weights = nullptr;
+        const hsddp::PWts *phase_weights = nullptr;
         int par = 0;  // which host count slot (host_counter[8 + 4 * par + 1]) its copy fills
     } iter_graph[8];
     int iter_graph_next = 0;
@@ -164,6 +165,20 @@ struct hsddp_handle_t {
     hsddp::Wts *weights_dev = nullptr, *weights_pin = nullptr;
     bool weights_stale = false;
     hipEvent_t weights_up = nullptr;
+    // per-phase weights (hsddp_set_phase_weights): the override flags [B][P] and rows [B][P] at the
+    // stride p.P — the source of truth, moved with the phases by hsddp_phases.cpp; both empty: no
+    // phase has an override (they are emptied when the last one leaves).  The device copy the
+    // per-phase instantiations read is the dense table of effective rows (override, else the robot's
+    // row, else desc.weights), [B][HSDDP_MAX_PHASES] rows allocated on first use so the pointer the
+    // iteration graphs freeze never moves, read at the stride p.P; it is uploaded from pinned staging
+    // when an override, a flag, a robot's row beneath or the phase map changed (sync_phase_weights);
+    // pw_up: that upload's event
+    // (rows as doubles [B][P][NW], the form hsddp_phases.cpp moves them in: a shift's result is swapped in)
+    std::vector<int> pw_set;
+    std::vector<double> pw;
+    hsddp::PWts *pw_dev = nullptr, *pw_pin = nullptr;
+    bool pw_stale = false;
+    hipEvent_t pw_up = nullptr;
 };
 static_assert(sizeof(hsddp_hkd_weights) == hsddp::NW * sizeof(double), "hsddp_hkd_weights: NW doubles, no padding");
 
@@ -214,6 +229,8 @@ inline HorizonView view_of(hsddp_handle h)
     v.terrain = h->terrain.empty() ? nullptr : h->terrain.data();
     v.fill[0] = h->desc.cparams.mu_fric; v.fill[1] = h->desc.cparams.ground_height;
     v.weights = h->weights.empty() ? nullptr : (const double *)h->weights.data();
+    v.pw_set = h->pw_set.empty() ? nullptr : h->pw_set.data();
+    v.pw = h->pw_set.empty() ? nullptr : h->pw.data();
     return v;
 }
 
@@ -234,7 +251,11 @@ int sync_terrain(hsddp_handle h);
 
 // the weight table the kernels' weights instantiations read (null: off, the plain instantiations);
 // whoever turns the table on allocates it first (ensure_weights_table), as with the terrain
-inline const Wts *weights_of(hsddp_handle h) { return h->weights.empty() ? nullptr : h->weights_dev; }
+// ... and the per-phase table of effective rows while a phase has an override
+inline WtsTab weights_of(hsddp_handle h)
+{
+    return {h->weights.empty() ? nullptr : h->weights_dev, h->pw_set.empty() ? nullptr : h->pw_dev};
+}
 // robot b's weights: its row, or the handle's
 inline const hsddp_hkd_weights &weights_of(hsddp_handle h, size_t b) { return h->weights.empty() ? h->desc.weights : h->weights[b]; }
 // hsddp_api.cpp: a row in the kernels' field order; the device table with its staging (allocated once);
@@ -244,6 +265,29 @@ void weights_row(const hsddp_hkd_weights &w, Wts &r);
 int ensure_weights_table(hsddp_handle h);
 int sync_weights(hsddp_handle h);
 bool weights_finite(const hsddp_hkd_weights &w);
+// phase i of robot b: its override, or the robot's row, or the handle's
+inline const hsddp_hkd_weights &weights_of(hsddp_handle h, size_t b, int i)
+{
+    const size_t q = b * (size_t)h->p.P + i;
+    return !h->pw_set.empty() && i < h->p.P && h->pw_set[q] ? *reinterpret_cast<const hsddp_hkd_weights *>(&h->pw[q * NW])
+                                                            : weights_of(h, b);
+}
+// hsddp_api.cpp: the per-phase device table with its staging (allocated once); the table brought up to
+// the host rows on the handle's stream (never inside a graph capture); the new host rows taken
+// (swapped in) after a layout change (hsddp_phases.cpp formed them); after any change of the flags:
+// both emptied when no override is left, the device table due
+int ensure_phase_weights_table(hsddp_handle h);
+int sync_phase_weights(hsddp_handle h);
+void adopt_phase_weights(hsddp_handle h, std::vector<int> &set, std::vector<double> &rows);
+void settle_phase_weights(hsddp_handle h);
+// every override gone (a new layout, w = NULL)
+inline void drop_phase_weights(hsddp_handle h)
+{
+    if (h->pw_set.empty()) return;
+    h->pw_set.clear();
+    h->pw.clear();
+    h->slots_fresh = false;
+}
 
 // phase of control slot kc in a layout
 inline int phase_of_control(const Layout &L, int kc)

@@ -206,6 +206,11 @@ static int shift_apply(hsddp_handle h, const ShiftPlan &plan, bool defer, int *o
     // the terrain rows follow the phases on the host (the old rows are read before the layouts change)
     std::vector<double> terrain;
     if (!h->terrain.empty()) shift_terrain(view_of(h), plan, Pnew, terrain);
+    // ... and the weight overrides (a phase the steps started has none)
+    const bool had_pw = !h->pw_set.empty();
+    std::vector<int> pw_set;
+    std::vector<double> pw_rows;
+    if (had_pw) shift_phase_weights(view_of(h), plan, Pnew, pw_set, pw_rows);
     std::vector<int> &smap = m.smap, &cmap = m.cmap, &rmap = m.rmap, &pmap = m.pmap, &nadd = m.nadd;
     HIPCHK(hipSetDevice(h->desc.device));
     Bufs &d = h->d;
@@ -301,6 +306,7 @@ static int shift_apply(hsddp_handle h, const ShiftPlan &plan, bool defer, int *o
         h->terrain.swap(terrain);
         h->terrain_stale = true;
     }
+    if (had_pw) adopt_phase_weights(h, pw_set, pw_rows);
     h->need_inputs = true;
     h->refs_on_device = false;  // built for the old layout
     h->ref_cols_stale = true;
@@ -612,6 +618,11 @@ extern "C" int hsddp_restart_elements(hsddp_handle h, const int *mask, const int
         for (int m = 0; m < n; ++m) put_terrain_rows(nullptr, 0, p.P, v.fill, &h->terrain[(size_t)list[m] * p.P * 2]);
         h->terrain_stale = true;
     }
+    if (!h->pw_set.empty()) {  // a new problem's cost objects are new: no overrides (the robot's row stays)
+        for (int m = 0; m < n; ++m)  // (in place: only the restarted robots' rows are written)
+            put_phase_weight_rows(nullptr, nullptr, 0, p.P, &h->pw_set[(size_t)list[m] * p.P], &h->pw[(size_t)list[m] * p.P * NW]);
+        settle_phase_weights(h);
+    }
     if (restride && (rc = h2d((void *)h->d.contacts, h->contacts.data(), h->contacts.size() * sizeof(int), h->stream)))
         return rc;
     // the window starts; references: at a new stride every element's are rebuilt; shared ones (every
@@ -824,7 +835,7 @@ static int move_elements(hsddp_handle dst, const MoveSource &src, int n, const i
     if (n == 0) return HSDDP_OK;  // nothing moves: nothing is launched, nothing changes
     Params &p = dst->p;
     const int B = p.B;
-    const RecordLayout R = record_layout(p.Kc, dst->S_cap, p.fp32);
+    const RecordLayout R = record_layout(p.Kc, dst->S_cap, p.fp32, true);
     int rc;
     // check: the two sides agree, both are settled, the indices
     const ElementKey kd = key_of(dst);
@@ -834,6 +845,7 @@ static int move_elements(hsddp_handle dst, const MoveSource &src, int n, const i
     }
     if ((rc = settled(dst, "destination"))) return rc;
     std::vector<ElementImport> in(n);
+    std::vector<PhaseOverrides> ov(n);
     bool at_init = true;
     int hist_need = 0;
     if (src.h) {
@@ -841,6 +853,7 @@ static int move_elements(hsddp_handle dst, const MoveSource &src, int n, const i
         for (int m = 0; m < n; ++m) {
             if (src.index[m] < 0 || src.index[m] >= vs.B) return fail(HSDDP_ERR_ARG, "source element index out of range");
             export_element(vs, src.index[m], in[m]);
+            export_overrides(vs, src.index[m], ov[m]);
         }
         at_init = src.h->reb_at_init;
         hist_need = src.h->p.hcap;  // (room for whatever a source element holds)
@@ -852,6 +865,7 @@ static int move_elements(hsddp_handle dst, const MoveSource &src, int n, const i
             if ((rc = compatible(hd.key, kd, true))) return rc;
             if (hd.hist_n < 0 || hd.hist_n > REC_HIST) return fail(HSDDP_ERR_ARG, "damaged element record");
             in[m] = hd.host;
+            std::memcpy(&ov[m], src.records + (size_t)m * R.bytes + R.pw, sizeof ov[m]);
             at_init = at_init && hd.reb_at_init != 0;
             hist_need = std::max(hist_need, hd.hist_n);
         }
@@ -890,6 +904,19 @@ static int move_elements(hsddp_handle dst, const MoveSource &src, int n, const i
         if (!weights_finite(w)) return fail(HSDDP_ERR_ARG, "an element's weight row holds a non-finite value");
     }
     if (brings_weights && (rc = ensure_weights_table(dst))) return rc;
+    // ... and its phase overrides hsddp_set_phase_weights'
+    bool brings_pw = false;
+    for (int m = 0; m < n; ++m) {
+        if (!ov[m].has) continue;
+        brings_pw = true;
+        for (int i = 0; i < in[m].L.P; ++i) {
+            if (!ov[m].set[i]) continue;
+            hsddp_hkd_weights w;
+            std::memcpy(&w, &ov[m].rows[(size_t)i * NW], sizeof w);
+            if (!weights_finite(w)) return fail(HSDDP_ERR_ARG, "an element's phase weight rows hold a non-finite value");
+        }
+    }
+    if (brings_pw && (rc = ensure_phase_weights_table(dst))) return rc;
     if (restride && !kd.has_table)
         return fail(HSDDP_ERR_UNSUPPORTED, "the move changes the destination's strides: its other elements' references "
                                            "are rebuilt from the table, and it has none");
@@ -1022,6 +1049,18 @@ static int move_elements(hsddp_handle dst, const MoveSource &src, int n, const i
             else dst->weights[list[m]] = dst->desc.weights;
         }
         dst->weights_stale = true;
+        dst->pw_stale = true;
+    }
+    // the phase overrides arrive with the robot's phases; a destination without any takes them up
+    if (brings_pw || !dst->pw_set.empty()) {
+        if (dst->pw_set.empty()) {
+            dst->pw_set.assign((size_t)B * p.P, 0);
+            dst->pw.assign((size_t)B * p.P * NW, 0.0);
+        }
+        for (int m = 0; m < n; ++m)
+            put_phase_weight_rows(ov[m].has ? ov[m].set : nullptr, ov[m].rows, in[m].L.P, p.P, &dst->pw_set[(size_t)list[m] * p.P],
+                                  &dst->pw[(size_t)list[m] * p.P * NW]);
+        settle_phase_weights(dst);
     }
     // the windows (at a new stride every element's references are rebuilt; the arriving elements'
     // rows then replace theirs) and the clocks
@@ -1066,7 +1105,7 @@ extern "C" int hsddp_copy_elements(hsddp_handle dst, hsddp_handle src, int n, co
 extern "C" size_t hsddp_element_record_bytes(const struct hsddp_handle_t *h)
 {
     if (!h) { fail(HSDDP_ERR_ARG, "null handle"); return 0; }
-    return record_layout(h->p.Kc, h->S_cap, h->p.fp32).bytes;
+    return record_layout(h->p.Kc, h->S_cap, h->p.fp32, true).bytes;
 }
 
 extern "C" int hsddp_export_elements(hsddp_handle h, int n, const int *index, void *records)
@@ -1078,7 +1117,7 @@ extern "C" int hsddp_export_elements(hsddp_handle h, int n, const int *index, vo
     const Params &p = h->p;
     for (int m = 0; m < n; ++m)
         if (index[m] < 0 || index[m] >= p.B) return fail(HSDDP_ERR_ARG, "element index out of range");
-    const RecordLayout R = record_layout(p.Kc, h->S_cap, p.fp32);
+    const RecordLayout R = record_layout(p.Kc, h->S_cap, p.fp32, true);
     HIPCHK(hipSetDevice(h->desc.device));
     HIPCHK(hipStreamSynchronize(h->stream));
     const size_t ib = ((size_t)n * sizeof(int) + 255) & ~(size_t)255;
@@ -1111,6 +1150,9 @@ extern "C" int hsddp_export_elements(hsddp_handle h, int n, const int *index, vo
         std::memcpy(&E, rec + R.el, sizeof E);
         hd.hist_n = E.hist_n;
         std::memcpy(rec, &hd, sizeof hd);
+        PhaseOverrides po;
+        export_overrides(v, index[m], po);
+        std::memcpy(rec + R.pw, &po, sizeof po);
         if (E.hist_n > REC_HIST) rc = HSDDP_ERR_UNSUPPORTED;
     }
     if (rc) return fail(rc, "an element holds more solver-info entries than a record has room for (256)");

@@ -125,6 +125,21 @@ static_assert(sizeof(Wts) == 48 * sizeof(double), "Wts: three 128-byte lines");
 static_assert(offsetof(Params, foot_term_grad) - offsetof(Params, qbase) == offsetof(Wts, foot_term_grad),
               "Wts: Params' weight fields in Params' order");
 
+// One phase's effective weights (hsddp_set_phase_weights): a row of the handle's device table
+// [B][P] at the phase stride — the phase's override, else its robot's row, else the handle's
+// weights.  A type of its own, so that a launcher's argument pack picks the per-phase instantiation
+// (TerrT's third mode) by the pointer it ends in.
+struct PWts {
+    Wts row;
+};
+// The weights a launcher reads: per-phase rows while a phase has an override, else per-robot rows
+// while that table is on, else neither (Params' weights).  with_flags_table(s) (hsddp_dispatch.h)
+// passes on the one that is set.
+struct WtsTab {
+    const Wts *robot = nullptr;
+    const PWts *phase = nullptr;
+};
+
 // one element deferred to the parallel retry: its index and the regularisation of its failed sweep
 struct RetryEntry {
     int b, pad;
@@ -253,21 +268,24 @@ struct Bufs {
 // weights: the per-robot weight rows [B] (hsddp_set_element_weights; the weights instantiations,
 // which read element b's row wherever the plain ones read Params' weight fields), or null: the
 // handle's weights in Params, the instantiations and arguments without rows.  Not in Bufs either.
+// While a phase has an override (hsddp_set_phase_weights) WtsTab::phase is the dense table of
+// effective rows [B][P] and the per-phase instantiations run; handles without overrides launch what
+// they launched before.
 
 // ---- hsddp_lq.hip: the LQ model (k_lq) and the terminal tasks (k_terminal) ----
-void launch_lq(const Params &p, const Bufs &d, const double *terrain, const Wts *weights, hipStream_t st);
+void launch_lq(const Params &p, const Bufs &d, const double *terrain, WtsTab weights, hipStream_t st);
 
 // ---- hsddp_sweep.hip, hsddp_linear.hip ----
-void launch_riccati(const Params &p, const Bufs &d, const Wts *weights, hipStream_t st);
-void launch_lin_rollout(const Params &p, const Bufs &d, const Wts *weights, hipStream_t st);
+void launch_riccati(const Params &p, const Bufs &d, WtsTab weights, hipStream_t st);
+void launch_lin_rollout(const Params &p, const Bufs &d, WtsTab weights, hipStream_t st);
 
 // ---- hsddp_rollout.hip: the forward line search ----
 // tix: the trial's index in the inner iteration's line search (-1: the initial rollout)
 // (last: this trial is the search's last step size — used when the rollout launch also decides)
 void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
-                    const double *terrain, const Wts *weights, hipStream_t st);
+                    const double *terrain, WtsTab weights, hipStream_t st);
 void launch_decide(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
-                   const double *terrain, const Wts *weights, hipStream_t st);
+                   const double *terrain, WtsTab weights, hipStream_t st);
 
 // ---- hsddp_outer.hip: the outer loop's updates and the element-state housekeeping ----
 // nominal rows of every element into buffer 0 (Bufs::sel bit 0 cleared), for host transfers

@@ -536,8 +536,8 @@ __global__ __launch_bounds__(64, 2) void k_lin_rollout(Params p, Bufs d, WP... w
         if (rowl) dx = dx + defg[(b * p.S + s0) * NX + r];
         if (st) d.dX[(b * p.S + s0) * NX + r] = dx;
         // lxx row r (HKDCost.cpp:32): diagonal + foot cross terms
-        lxx_row(p, wt.w(p, b), R.pc, r, R.lx);
-        R.ru = rowl ? (real)(p.dt * r_diag(wt.w(p, b), r)) : (real)0;
+        lxx_row(p, wt.w(p, b, i), R.pc, r, R.lx);
+        R.ru = rowl ? (real)(p.dt * r_diag(wt.w(p, b, i), r)) : (real)0;
         // control r has a gain row only when its B column is non-zero (KCW layout)
         const bool stl = contact(R.pc, (rr % HC) / 3) != 0;
         R.cpl = rowl && (rr < HC ? stl : !stl);
@@ -571,7 +571,7 @@ __global__ __launch_bounds__(64, 2) void k_lin_rollout(Params p, Bufs d, WP... w
 #endif
     if (r == 0 && act) merit_step(p, E, v1, v2);
 }
-void launch_lin_rollout(const Params &p, const Bufs &d, const Wts *weights, hipStream_t st)
+void launch_lin_rollout(const Params &p, const Bufs &d, WtsTab weights, hipStream_t st)
 {
     const dim3 g((unsigned)(p.elem_layout ? p.n_pairs : (p.B + 1) / 2));
     with_flags_table([&](auto f32, auto el, auto... wp) {

@@ -169,8 +169,8 @@ DEV void terminal_task(const Params &p, const Bufs &d, const TR &terr, TermLds &
     }
     wave_sync();
     // the robot's weights: Params / its row for compile-time fields, runtime-indexed ones in place
-    const auto &w = terr.w(p, b);
-    const auto &kp = terr.wk(b);
+    const auto &w = terr.w(p, b, i);
+    const auto &kp = terr.wk(b, i);
     double *rec = d.term + ((size_t)b * p.P + i) * TW;
     if (t == 0) {  // the phase's terminal cost at X[N] (SinglePhase::compute_cost's last term) for k_lq's slot sums
         double tv;
@@ -378,7 +378,7 @@ __global__ __launch_bounds__(256, FWD_MINB) void k_lq(Params p, Bufs d, TR... tr
     const double *ur = ref_ptr(p, d.ref_u, b, s, NU);
     const double *dl = d.reb_delta + ((size_t)b * p.Kc + kc) * 20, *ep = d.reb_eps + ((size_t)b * p.Kc + kc) * 20;
     const double mu = terr.mu(p, b, i);
-    const auto &wr = terr.w(p, b);  // the robot's weights
+    const auto &wr = terr.w(p, b, i);  // the weights of the knot's phase
     if (SLOTS) {  // the running cost (else the last rollout's: same trajectory, same parameters)
         double viol;
         d.slot_cost[(size_t)b * p.S + s] = running_cost(p, wr, mu, c, x, u, xr, ur, pf, dl, ep, viol, ovr);
@@ -456,7 +456,7 @@ __global__ __launch_bounds__(128, 4) void k_terminal(Params p, Bufs d, TR... tr)
     terminal_wave<EL>(p, d, terrain_of(tr...), S + w * TERM_TPW, (long)blockIdx.x * 2 + w, threadIdx.x & 63);
 }
 
-void launch_lq(const Params &p, const Bufs &d, const double *terrain, const Wts *weights, hipStream_t st)
+void launch_lq(const Params &p, const Bufs &d, const double *terrain, WtsTab weights, hipStream_t st)
 {
     // the terminal waves: a launch of their own (five waves per SIMD), or, for a small batch whose
     // knot and terminal blocks all fit the chip at once (C1: one robot), the blocks after k_lq's

@@ -297,6 +297,32 @@ void shift_terrain(const HorizonView &v, const ShiftPlan &plan, int P, std::vect
     }
 }
 
+// ---- per-phase weights ------------------------------------------------------------------------------
+void put_phase_weight_rows(const int *set, const double *rows, int n, int P, int *out_set, double *out_rows)
+{
+    for (int i = 0; i < P; ++i) {
+        const bool on = set && i < n && set[i];
+        out_set[i] = on ? 1 : 0;
+        if (on) std::copy_n(rows + (size_t)i * NW, NW, out_rows + (size_t)i * NW);
+        else std::fill_n(out_rows + (size_t)i * NW, NW, 0.0);
+    }
+}
+
+void shift_phase_weights(const HorizonView &v, const ShiftPlan &plan, int P, std::vector<int> &set, std::vector<double> &rows)
+{
+    set.assign((size_t)v.B * P, 0);
+    rows.assign((size_t)v.B * P * NW, 0.0);
+    for (int b = 0; b < v.B; ++b) {
+        const std::vector<ShiftPhase> &ph = plan.phs[plan.map_id[b]];
+        for (int i = 0; i < (int)ph.size() && i < P; ++i) {
+            const int src = ph[i].src;
+            if (src < 0 || src >= v.P || !v.pw_set[(size_t)b * v.P + src]) continue;
+            set[(size_t)b * P + i] = 1;
+            std::copy_n(&v.pw[((size_t)b * v.P + src) * NW], NW, &rows[((size_t)b * P + i) * NW]);
+        }
+    }
+}
+
 // ---- references ------------------------------------------------------------------------------------
 std::vector<float> clock_starts(const Layout &L, float dt_sim)
 {
@@ -547,6 +573,15 @@ void export_element(const HorizonView &v, int b, ElementImport &out)
     if (v.terrain) std::copy_n(&v.terrain[(size_t)b * v.P * 2], L.P * 2, out.terrain);
     out.has_weights = v.weights ? 1 : 0;
     if (v.weights) std::copy_n(&v.weights[(size_t)b * NW], NW, out.weights);
+}
+
+void export_overrides(const HorizonView &v, int b, PhaseOverrides &out)
+{
+    const Layout &L = v.layout(b);
+    std::memset(&out, 0, sizeof out);
+    if (!v.pw_set) return;
+    put_phase_weight_rows(&v.pw_set[(size_t)b * v.P], &v.pw[(size_t)b * v.P * NW], L.P, MAXP, out.set, out.rows);
+    for (int i = 0; i < L.P; ++i) out.has |= out.set[i];
 }
 
 int plan_import_batch(const HorizonView &v, const std::vector<int> &list, const ElementImport *in, RestartBatch &r,

@@ -126,6 +126,8 @@ struct HorizonView {
     const double *terrain;  // [B][P][2] (mu, ground) per phase (hsddp_set_terrain), or null: off
     double fill[2];         // the handle's cparams pair: the row of a phase without one of its own
     const double *weights;  // [B][NW] per-robot weight rows (hsddp_set_element_weights), or null: off
+    const int *pw_set;      // [B][P] a phase's weights are an override (hsddp_set_phase_weights), or null: none
+    const double *pw;       // [B][P][NW] the override rows (read where pw_set is set)
 
     const Layout &layout(int b) const { return lays ? lays[b] : *shared; }
     const int *reach_of(int b) const { return lays ? reach + (size_t)b * MAXP : reach; }
@@ -168,6 +170,16 @@ void shifted_layouts(const ShiftPlan &plan, std::vector<Layout> &lays, std::vect
 void shift_terrain(const HorizonView &v, const ShiftPlan &plan, int P, std::vector<double> &out);
 // one element's rows at stride P: its own n rows (null: fill), fill past them
 void put_terrain_rows(const double *rows, int n, int P, const double *fill, double *out);
+
+// ---- per-phase weights ------------------------------------------------------------------------------
+// An override (hsddp_set_phase_weights) belongs to its phase's cost objects.  The view's flags [B][P]
+// and rows [B][P][NW] after a shift plan, at the new stride P: an old phase keeps its flag and row;
+// a phase the steps started has none (create_problem_one_phase constructs new cost objects — where
+// the terrain row of a new phase repeats the one before it), nor has a phase without a source or one
+// past an element's phases.  Rows without a flag are zero.  (Reads the view's pw_set and pw only.)
+void shift_phase_weights(const HorizonView &v, const ShiftPlan &plan, int P, std::vector<int> &set, std::vector<double> &rows);
+// one element's flags and rows at stride P: its own n (null: none), none past them
+void put_phase_weight_rows(const int *set, const double *rows, int n, int P, int *out_set, double *out_rows);
 
 // ---- references ------------------------------------------------------------------------------------
 // the phases' start times on the float clock of HKDProblem::initialization (t += dt_sim per knot)
@@ -279,8 +291,16 @@ struct ElementImport {
     int has_weights;              // the source's weight table was on: weights holds the robot's row
     double weights[NW];           // (the fields of hsddp_hkd_weights, in order)
 };
+// ... and its phase overrides (hsddp_set_phase_weights), carried beside it: a record holds them in a
+// block of its own between the header and the payload (hsddp_elements.h)
+struct PhaseOverrides {
+    int has;                      // the element has overrides: set flags them, rows holds their rows
+    int set[MAXP];
+    double rows[MAXP * NW];       // (zero where set is 0)
+};
 // element b of the view
 void export_element(const HorizonView &v, int b, ElementImport &out);
+void export_overrides(const HorizonView &v, int b, PhaseOverrides &out);
 // The batch's side of slot list[m] becoming the element in[m]: plan_restart_batch's decisions (one,
 // restride, in_place, strides, contact and duration rows, window starts; patch_pairs follows as
 // there) with each listed element's layout, reach flags, rows, window start and clock taken from

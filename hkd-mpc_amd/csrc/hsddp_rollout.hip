@@ -105,9 +105,9 @@ DEV void finish_slot(const Params &p, const Bufs &d, const TR &terr, const L_ &L
 {
     finish_defect(p, d, b, s, k, x, xs);
     if (k == L.N(i))
-        finish_terminal(p, d, terr.w(p, b), terr.ground(p, b, i), b, s, i, c, cn, x);
+        finish_terminal(p, d, terr.w(p, b, i), terr.ground(p, b, i), b, s, i, c, cn, x);
     else
-        finish_running(p, d, terr.w(p, b), terr.mu(p, b, i), b, s, L.k0(i) + k, c, x, u);
+        finish_running(p, d, terr.w(p, b, i), terr.mu(p, b, i), b, s, L.k0(i) + k, c, x, u);
 }
 
 // trial tix > 0 of an inner iteration runs only when an element is still searching after trial
@@ -274,7 +274,7 @@ DEV void rollout_boundary(const Params &p, const Bufs &d, const TR &terr, double
         finish_defect(p, d, b, s0, 0, x, xs);
     }
     trial(sN, x);
-    finish_terminal(p, d, terr.w(p, b), terr.ground(p, b, i), b, sN, i, c, cn, x);
+    finish_terminal(p, d, terr.w(p, b, i), terr.ground(p, b, i), b, sN, i, c, cn, x);
 }
 
 // WIDE: p.S >= RW (instantiated apart: a wave's 64 slots then belong to at most two elements, and
@@ -368,7 +368,7 @@ DEV void rollout_block(const Params &p, const Bufs &d, const TR &terr, double ep
         d2 *ug = (d2 *)(kubuf(tb) + kq * NU);
 #pragma unroll
         for (int j = 0; j < NU / 2; ++j) ug[j] = d2{u[2 * j], u[2 * j + 1]};
-        finish_running<true>(p, d, terr.w(p, b), terr.mu(p, b, i), b, s, L.k0(i) + k, c, x, u);
+        finish_running<true>(p, d, terr.w(p, b, i), terr.mu(p, b, i), b, s, L.k0(i) + k, c, x, u);
     }
     RSTAMP(4);
     // u_prev: the previous slot's control row is the previous lane's (k > 0: slot s - 1 is a
@@ -547,7 +547,7 @@ DEV void ss_phase(const Params &p, const Bufs &d, const TR &terr, int b, int i, 
         for (int j = 0; j < NX; ++j) xg[j] = x[j];
         if (k > 0 || x_init) finish_defect(p, d, b, s, k, x, k > 0 ? xs : x);
         if (k == N) {
-            finish_terminal(p, d, terr.w(p, b), terr.ground(p, b, i), b, s, i, c, cn, x);
+            finish_terminal(p, d, terr.w(p, b, i), terr.ground(p, b, i), b, s, i, c, cn, x);
             break;
         }
         // U = Ubar + eps dU + K (X - Xbar) (SinglePhase.cpp:200), K from the 12 coupled gain rows
@@ -564,7 +564,7 @@ DEV void ss_phase(const Params &p, const Bufs &d, const TR &terr, int b, int i, 
         }
         double *ug = U + (kb + kc) * NU;
         for (int j = 0; j < NU; ++j) { u[j] = add_step(ub[j], eps, du[j]) + u[j]; ug[j] = u[j]; }
-        finish_running(p, d, terr.w(p, b), terr.mu(p, b, i), b, s, kc, c, x, u);
+        finish_running(p, d, terr.w(p, b, i), terr.mu(p, b, i), b, s, kc, c, x, u);
         hkd_step(x, u, cd, p.dt, xs);
     }
 }
@@ -666,7 +666,7 @@ DEV void diverged_fixup(const Params &p, const Bufs &d, const TR &terr, const La
         // kernel's registers; the arithmetic is the slot kernels')
         const double *x = XT + (sb + s) * NX;
         if (k == L.N(ip)) {
-            finish_terminal(p, d, terr.w(p, b), terr.ground(p, b, ip), b, s, ip, c, cn, x, true);
+            finish_terminal(p, d, terr.w(p, b, ip), terr.ground(p, b, ip), b, s, ip, c, cn, x, true);
             continue;
         }
         const int kc = L.k0(ip) + k;
@@ -676,7 +676,7 @@ DEV void diverged_fixup(const Params &p, const Bufs &d, const TR &terr, const La
         const double *ur = ref_ptr(p, d.ref_u, b, s, NU);
         const double *dl = d.reb_delta + (kq + kc) * 20, *ep = d.reb_eps + (kq + kc) * 20;
         double viol;
-        d.slot_cost[sb + s] = running_cost(p, terr.w(p, b), terr.mu(p, b, ip), c, x, u, xr, ur, pf, dl, ep, viol, ovr);
+        d.slot_cost[sb + s] = running_cost(p, terr.w(p, b, ip), terr.mu(p, b, ip), c, x, u, xr, ur, pf, dl, ep, viol, ovr);
         d.slot_viol[sb + s] = viol;
     }
 }
@@ -860,7 +860,7 @@ static bool fused_decide(const Params &p)
 }
 
 void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
-                    const double *terrain, const Wts *weights, hipStream_t st)
+                    const double *terrain, WtsTab weights, hipStream_t st)
 {
     if (p.ms0) {  // single shooting: every knot simulated (k_rollout_ss)
         with_flags_tables([&](auto el, auto... tr) {
@@ -883,7 +883,7 @@ void launch_rollout(const Params &p, const Bufs &d, double eps, int last, int in
         }, terrain, weights, p.elem_layout);
 }
 void launch_decide(const Params &p, const Bufs &d, double eps, int last, int init, int tix, const int *budget,
-                   const double *terrain, const Wts *weights, hipStream_t st)
+                   const double *terrain, WtsTab weights, hipStream_t st)
 {
     if (fused_decide(p)) return;  // decided by the rollout launch
     with_flags_tables([&](auto el, auto... tr) {

@@ -15,7 +15,7 @@ struct SimArgs {
     double *X, *U;              // [B][M][n_steps][24] zeroed by the caller, or null
 };
 // terrain: the per-phase (mu, ground) pairs min_grf / max_td are taken against, or null (hsddp_internal.h)
-void launch_simulate_policy(const Params &p, const Bufs &d, const SimArgs &a, const double *terrain, const Wts *weights,
+void launch_simulate_policy(const Params &p, const Bufs &d, const SimArgs &a, const double *terrain, WtsTab weights,
                             hipStream_t st);
 
 }  // namespace hsddp

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(64) void k_simulate_policy(Params p, Bufs d, SimArg
                 live = false;
             } else {
                 const double *xr = sh + PK_XR, *ur = sh + PK_UR, *pf = sh + PK_PF;
-                const auto &w = terr.w(p, b);  // the robot's weights
+                const auto &w = terr.w(p, b, i);  // the weights of the knot's phase
                 const double lt = cost_tracking(w, c, x, xr), lu = cost_control(w, u, ur), lf = cost_foot(w, c, x, xr, pf);
                 cost += cost_combine(p, c, lt, lu, lf, 0.0);  // (no ReB term)
                 const double mu = terr.mu(p, b, i);
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(64) void k_simulate_policy(Params p, Bufs d, SimArg
     }
 }
 
-void launch_simulate_policy(const Params &p, const Bufs &d, const SimArgs &a, const double *terrain, const Wts *weights,
+void launch_simulate_policy(const Params &p, const Bufs &d, const SimArgs &a, const double *terrain, WtsTab weights,
                             hipStream_t st)
 {
     const unsigned grid = (unsigned)p.B * (unsigned)((a.M + 63) / 64);

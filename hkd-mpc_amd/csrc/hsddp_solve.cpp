@@ -89,7 +89,8 @@ static int solve_check(hsddp_handle h)
     HIPCHK(hipSetDevice(h->desc.device));
     h->sim_fresh = false;  // the policy changes: a simulation held is of the old one
     if (int rc = sync_terrain(h)) return rc;
-    return sync_weights(h);
+    if (int rc = sync_weights(h)) return rc;
+    return sync_phase_weights(h);
 }
 
 static std::vector<double> ls_steps(double alpha)
@@ -173,7 +174,7 @@ static int graph_launch(hsddp_handle h, const std::vector<double> &trials, int p
     for (auto &c : h->iter_graph)
         if (c.exec && c.par == par && !std::memcmp(&c.p, &pl, sizeof(Params)) &&
             !std::memcmp(&c.d, &h->d, sizeof(Bufs)) && c.alpha == h->opt.alpha && c.budget == budget_of(h) &&
-            c.terrain == terrain_of(h) && c.weights == weights_of(h))
+            c.terrain == terrain_of(h) && c.weights == weights_of(h).robot && c.phase_weights == weights_of(h).phase)
             hit = &c;
     if (!hit) {
         auto &g = h->iter_graph[h->iter_graph_next];
@@ -205,7 +206,8 @@ static int graph_launch(hsddp_handle h, const std::vector<double> &trials, int p
         g.alpha = h->opt.alpha;
         g.budget = budget_of(h);
         g.terrain = terrain_of(h);  // (null: terrain off — other instantiations, other arguments)
-        g.weights = weights_of(h);  // (null: the table off)
+        g.weights = weights_of(h).robot;  // (null: the table off)
+        g.phase_weights = weights_of(h).phase;  // (null: no phase has an override)
         g.par = par;
         hit = &g;
     }

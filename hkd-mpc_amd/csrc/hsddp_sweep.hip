@@ -221,8 +221,8 @@ struct Phase {
 template <typename real, typename ItemT, typename WT>
 DEV void load_phase(const Params &p, const Bufs &d, ItemT &I, int b, int i, int pp, Phase<real> &ph, const WT &wt)
 {
-    const auto &ww = wt.w(p, b);
-    const auto &wk = wt.wk(b);  // (runtime field indices)
+    const auto &ww = wt.w(p, b, i);
+    const auto &wk = wt.wk(b, i);  // (runtime field indices)
     const int *cs = d.contacts + ((size_t)b * (p.P + 1) + i) * 4;
     int c[4];
 #pragma unroll
@@ -1470,7 +1470,7 @@ static int sweep_wpb(const Params &p)
 
 // k_riccati for one precision and wave count per workgroup (axes that are not flags: fp32 has W = 1 only)
 template <typename real, int W>
-static void launch_sweep(const Params &p, const Bufs &d, const Wts *weights, dim3 gw, int masks, hipStream_t st)
+static void launch_sweep(const Params &p, const Bufs &d, WtsTab weights, dim3 gw, int masks, hipStream_t st)
 {
     with_flags_table([&](auto el, auto dv, auto... wp) {
         hipLaunchKernelGGL((k_riccati<real, decltype(el)::value, decltype(dv)::value, W>), gw, dim3(64 * W), 0, st, p, d, masks, wp...);
@@ -1478,7 +1478,7 @@ static void launch_sweep(const Params &p, const Bufs &d, const Wts *weights, dim
 }
 // the parallel retries of the elements whose first sweep failed, then the first success of each
 template <typename real>
-static void launch_retry(const Params &p, const Bufs &d, const Wts *weights, int masks, hipStream_t st)
+static void launch_retry(const Params &p, const Bufs &d, WtsTab weights, int masks, hipStream_t st)
 {
     const dim3 gr((unsigned)(p.retry_cap * (p.retry_m + (p.retry_m & 1)) / 2)), gs((unsigned)p.retry_cap);
     with_flags_table([&](auto el, auto dv, auto... wp) {
@@ -1487,7 +1487,7 @@ static void launch_retry(const Params &p, const Bufs &d, const Wts *weights, int
     hipLaunchKernelGGL(k_riccati_select<real>, gs, dim3(64), 0, st, p, d);
 }
 
-void launch_riccati(const Params &p, const Bufs &d, const Wts *weights, hipStream_t st)
+void launch_riccati(const Params &p, const Bufs &d, WtsTab weights, hipStream_t st)
 {
     // (the retry list count is zeroed by the k_lq launch just before, in its first terminal task)
     const dim3 g1((unsigned)(p.elem_layout ? p.n_pairs : (p.B + 1) / 2));

@@ -196,6 +196,33 @@ public:
         chk(hsddp_set_element_weights(h, rows.data(), mask.data()));
     }
 
+    // Per-phase cost weights (hsddp_set_phase_weights): phase `phase` of the robot's current horizon
+    // takes w as its override from the next solve on, as a cost object of that phase would hold it.
+    // The override moves with its phase through the ticks and leaves with it; a phase the horizon
+    // appends has none and reads the robot's row (set_weights) or the settings'; restart() drops the
+    // robot's overrides.  Call between ticks.
+    void set_phase_weights(int robot, int phase, const hsddp_hkd_weights &w)
+    {
+        if (robot < 0 || robot >= B) throw std::runtime_error("set_phase_weights: no such robot");
+        wait();
+        std::lock_guard<std::mutex> lk(mpc_mutex);
+        int P = 0, S = 0;
+        chk(hsddp_get_strides(h, &P, &S));
+        std::vector<int> np((size_t)B, P);
+        chk(hsddp_get_element_layouts(h, np.data(), nullptr, nullptr, nullptr));
+        if (phase < 0 || phase >= np[(size_t)robot]) throw std::runtime_error("set_phase_weights: the robot has no such phase");
+        // the C ABI takes [B][P] arrays and reads only the masked entry: buffers kept from call to
+        // call (grown at a new stride), one row written and one flag set and cleared again
+        const size_t n = (size_t)B * P, q = (size_t)robot * P + phase;
+        if (pw_rows.size() < n) pw_rows.resize(n);
+        if (pw_mask.size() < n) pw_mask.resize(n, 0);
+        pw_rows[q] = w;
+        pw_mask[q] = 1;
+        const int rc = hsddp_set_phase_weights(h, pw_rows.data(), pw_mask.data());
+        pw_mask[q] = 0;
+        chk(rc);
+    }
+
     // HKDMPCSolver::mpcdata_lcm_handler (HKDMPC.cpp:166-200): msgs[B]
     void mpcdata_lcm_handler(const std::vector<hkd_data_lcmt> &msgs)
     {
@@ -425,6 +452,8 @@ private:
     std::vector<int> pending_robots, pending_windows;  // restart(): applied by the next update()
     std::vector<hkd_data_lcmt> pending_states;
     std::mutex mpc_mutex;
+    std::vector<hsddp_hkd_weights> pw_rows;  // set_phase_weights' [B][P] arguments (mask all zero between calls)
+    std::vector<int> pw_mask;
     std::thread worker;
     std::exception_ptr worker_error;
     Publisher publish;

@@ -25,6 +25,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdio>
+#include <cstddef>
 #include <cstring>
 #include <deque>
 #include <functional>
@@ -1359,7 +1360,16 @@ public:
         // touchdown constraints' ground height; empty when the phases agree (desc.cparams carries the
         // pair, as it does for a handle without terrain)
         std::vector<double> mu, ground;
+        // per-phase weights (hsddp_set_phase_weights) [P]: the phases' own rows and which of them
+        // differ from desc.weights (those go to the handle as overrides); empty when none does
+        std::vector<hsddp_hkd_weights> phase_weights;
+        std::vector<int> phase_weights_set;
     };
+    // Phases whose cost objects carry different weights: true — each phase's row goes to the handle
+    // as an override (hsddp_set_phase_weights), as the reference runs one HKDTrackingCost and one
+    // HKDFootPlaceReg per phase; false (the default, the behaviour before per-phase weights) —
+    // describe() refuses them by name.
+    bool per_phase_weights = false;
     Problem describe();
 
     T get_actual_cost() { return actual_cost; }
@@ -1497,9 +1507,11 @@ private:
     static bool read_dynamics_partial(const Phase &ph, Bound &b);
     static int read_reset(const Phase &ph, Bound &b);  // 0: none registered, 1: read, -1: not HKDReset
     void write_back_constraints(const Problem &pr);
+    // (rows: every phase's own row, for hsddp_set_phase_weights where it differs from the returned one)
     static hsddp_hkd_weights derive_weights(const std::vector<hsddp_facade::CostSpec> &track,
                                             const std::vector<hsddp_facade::CostSpec> &foot,
-                                            const std::vector<int> &contacts);
+                                            const std::vector<int> &contacts,
+                                            std::vector<hsddp_hkd_weights> *rows = nullptr);
 
     std::deque<std::shared_ptr<SinglePhaseBase<T>>> phases;
     int n_phases = 0, device = 0;
@@ -1585,15 +1597,21 @@ int MultiPhaseDDP<T>::read_reset(const Phase &ph, Bound &b)
     return 1;
 }
 
-// One hsddp_hkd_weights that reproduces every phase's effective diagonals bit for bit (the device
-// holds one weight set per handle and masks it by each phase's contact).  Terms holding their weights
-// as hsddp_hkd_weights (hkd::) give them directly; for the reference's classes (Q, R, Qf, Qfoot
-// matrices) the gains keep their default and each scale is the quotient that reproduces the product
-// the device forms.
+// The handle's hsddp_hkd_weights and one row per phase (rows) that reproduces that phase's effective
+// diagonals bit for bit: in the reference the weights belong to each phase's cost objects
+// (HKDProblem.cpp:243-252), the device masks a row by its phase's contact.  Terms holding their
+// weights as hsddp_hkd_weights (hkd::) give them directly; for the reference's classes (Q, R, Qf,
+// Qfoot matrices) the gains keep their default and each scale is the quotient that reproduces the
+// product the device forms, phase by phase; a field a phase's contact masks out (qJ and its Qf scale
+// on a stance leg, the foot weights without a stance leg) is the handle-wide derivation's.  The
+// handle-wide set is the first phase's, completed from the first later phase that shows a masked
+// field.  A phase whose row equals it needs no override (describe()).  Refused: what no row can
+// express — a non-diagonal weight (device_spec), qJ weight on a stance leg.
 template <typename T>
 hsddp_hkd_weights MultiPhaseDDP<T>::derive_weights(const std::vector<hsddp_facade::CostSpec> &track,
                                                    const std::vector<hsddp_facade::CostSpec> &foot,
-                                                   const std::vector<int> &contacts)
+                                                   const std::vector<int> &contacts,
+                                                   std::vector<hsddp_hkd_weights> *rows)
 {
     hsddp_hkd_weights w;
     hsddp_default_weights(&w);
@@ -1645,19 +1663,51 @@ hsddp_hkd_weights MultiPhaseDDP<T>::derive_weights(const std::vector<hsddp_facad
     }
     w.foot_term_cost = foot[0].foot_term_cost;
     w.foot_term_grad = foot[0].foot_term_grad;
-    // every phase's diagonals as the device forms them from w
+    // every phase's own row, and its diagonals as the device forms them from it
     for (int i = 0; i < P; ++i) {
+        hsddp_hkd_weights wi = w;
+        const int *c = &contacts[4 * i];
+        if (track[i].exact) {
+            const hsddp_hkd_weights &e = *track[i].exact;
+            std::memcpy(wi.q_eul, e.q_eul, sizeof wi.q_eul); std::memcpy(wi.q_pos, e.q_pos, sizeof wi.q_pos);
+            std::memcpy(wi.q_omega, e.q_omega, sizeof wi.q_omega); std::memcpy(wi.q_v, e.q_v, sizeof wi.q_v);
+            wi.q_qJ = e.q_qJ; std::memcpy(wi.qf_scale, e.qf_scale, sizeof wi.qf_scale); wi.qf_gain = e.qf_gain;
+            wi.r_grf = e.r_grf; wi.r_qJd = e.r_qJd;
+        } else {
+            const double *q = track[i].q;
+            for (int a = 0; a < 3; ++a) { wi.q_eul[a] = q[a]; wi.q_pos[a] = q[3 + a]; wi.q_omega[a] = q[6 + a]; wi.q_v[a] = q[9 + a]; }
+            wi.r_grf = track[i].r[0];
+            wi.r_qJd = track[i].r[12];
+            for (int l = 0; l < 4; ++l)
+                if (!c[l]) { wi.q_qJ = q[12 + 3 * l]; break; }
+            for (int j = 0; j < 24; ++j) {
+                if (q[j] == 0) continue;
+                const double tq = track[i].qf[j], s0 = tq / q[j] / wi.qf_gain;
+                for (double sc : {w.qf_scale[j], s0, std::nextafter(s0, 1e300), std::nextafter(s0, -1e300)})
+                    if (wi.qf_gain * sc * q[j] == tq) { wi.qf_scale[j] = sc; break; }
+            }
+        }
+        if (foot[i].exact) {
+            const hsddp_hkd_weights &e = *foot[i].exact;
+            std::memcpy(wi.foot_w, e.foot_w, sizeof wi.foot_w);
+            wi.foot_gain = e.foot_gain;
+        } else {
+            int l = 0;
+            while (l < 4 && !c[l]) ++l;
+            for (int a = 0; a < 3 && l < 4; ++a) wi.foot_w[a] = factor(wi.foot_gain, foot[i].qfoot[3 * l + a], w.foot_w[a]);
+        }
+        wi.foot_term_cost = foot[i].foot_term_cost;
+        wi.foot_term_grad = foot[i].foot_term_grad;
         double q[24], r[24], qf[24], qfoot[12];
-        hsddp_facade::device_diagonals(w, &contacts[4 * i], q, r, qf, qfoot);
+        hsddp_facade::device_diagonals(wi, c, q, r, qf, qfoot);
         for (int j = 0; j < 24; ++j)
             if (q[j] != track[i].q[j] || r[j] != track[i].r[j] || qf[j] != track[i].qf[j])
-                refuse(i, "tracking weights (Q, R, Qf) differ from the other phases' or are not the HKD pattern "
-                          "(diagonal, qJ weighted on swing legs only): one device handle holds one weight set");
+                refuse(i, "tracking weights (Q, R, Qf) are not the HKD pattern (diagonal, one weight per field group, qJ "
+                          "weighted on swing legs only): no row of HKD weights reproduces them");
         for (int j = 0; j < 12; ++j)
             if (qfoot[j] != foot[i].qfoot[j])
-                refuse(i, "foot-placement weights (Qfoot) differ from the other phases' or are not the HKD pattern");
-        if (foot[i].foot_term_cost != w.foot_term_cost || foot[i].foot_term_grad != w.foot_term_grad)
-            refuse(i, "foot-placement terminal factors differ from the other phases'");
+                refuse(i, "foot-placement weights (Qfoot) are not the HKD pattern (one weight per axis, on stance legs only)");
+        if (rows) rows->push_back(wi);
     }
     return w;
 }
@@ -1842,7 +1892,30 @@ typename MultiPhaseDDP<T>::Problem MultiPhaseDDP<T>::describe()
             (foot[i].foot_rows >= 0 && foot[i].foot_rows != N + 1))
             refuse(i, "reference tables must match the horizon (x_ref and foot_ref: N + 1 rows, u_ref: at least N)");
     }
-    desc.weights = derive_weights(track, foot, pr.contacts);
+    // The cost objects are the source of truth at every solve: a phase whose row differs from the
+    // handle's takes it as an override, so an MPC loop carries per-phase weights from tick to tick
+    // with the phases.  (The handle's set follows the first phase; when that changes, solve() makes
+    // a new handle once, as for terrain above.)
+    {
+        std::vector<hsddp_hkd_weights> rows;
+        desc.weights = derive_weights(track, foot, pr.contacts, &rows);
+        std::vector<int> set(P, 0);
+        bool any = false;
+        for (int i = 0; i < P; ++i) any = (set[i] = std::memcmp(&rows[i], &desc.weights, sizeof desc.weights) != 0) || any;
+        // (off by default, so that a caller who relied on the refusal of differing phases keeps it)
+        for (int i = 0; i < P && !per_phase_weights; ++i) {
+            if (!set[i]) continue;
+            const hsddp_hkd_weights &a = rows[i], &b = desc.weights;
+            const bool foot_only = !std::memcmp(&a, &b, offsetof(hsddp_hkd_weights, foot_w));
+            refuse(i, std::string(foot_only ? "foot-placement weights (Qfoot, terminal factors)" : "tracking weights (Q, R, Qf)") +
+                          " differ from the other phases': set per_phase_weights = true to give every phase its own "
+                          "weight row (hsddp_set_phase_weights); without it one device handle holds one weight set");
+        }
+        if (any) {
+            pr.phase_weights.swap(rows);
+            pr.phase_weights_set.swap(set);
+        }
+    }
     hsddp_pack::layout(trajs, desc.horizons, desc.dt, pr.S, pr.Kc);
     // per-knot ReB parameters of the GRF constraints (initialize_params ran: its own, else the spec's)
     pr.reb_delta.assign((size_t)pr.Kc * 20, desc.cparams.grf_delta);
@@ -1977,6 +2050,8 @@ void MultiPhaseDDP<T>::solve(HSDDP_OPTION option)
     // every tick: the reference's update creates new constraint objects (hsddp_set_layout above
     // turned the last tick's terrain off)
     if (!pr.mu.empty()) check(hsddp_set_terrain(handle, pr.mu.data(), pr.ground.data()));
+    // ... and new cost objects (hsddp_set_layout dropped the last tick's overrides)
+    if (!pr.phase_weights.empty()) check(hsddp_set_phase_weights(handle, pr.phase_weights.data(), pr.phase_weights_set.data()));
     hsddp_stats st;
     check(hsddp_solve(handle, &st));
     // the constraint objects keep the parameters the solve's AL / ReB updates left (the next MPC

@@ -377,6 +377,45 @@ class Solver:
             out.append(w)
         return out
 
+    def set_phase_weights(self, weights, mask=None) -> None:
+        """Per-phase cost weights (hsddp_set_phase_weights): weights is a float64 array [B][P][46] of
+        the rows' fields in the structure's order or a ctypes array ((hsddp.Weights * P) * B), P the
+        phase stride (Solver.P); phase i of robot b with mask[b][i] != 0 (mask None: every phase
+        the robot has) takes weights[b][i] as its override, the others keep what they have.  A phase
+        reads its override, else the robot's row (set_element_weights), else the handle's weights.
+        None drops every override.  An override moves with its phase through shift and advance; an
+        appended phase has none; restart_elements drops a restarted robot's; copy / export / import
+        carry them.  Call between ticks."""
+        if weights is None:
+            check(lib().hsddp_set_phase_weights(self._h, None, None))
+            return
+        P = self.P
+        nf = C.sizeof(Weights) // 8
+        if isinstance(weights, np.ndarray):
+            rows = np.ascontiguousarray(weights, dtype=np.float64)
+            if rows.shape != (self.B, P, nf):
+                raise HSDDPError(f"weights: shape {rows.shape}, expected ({self.B}, {P}, {nf})")
+            addr = rows.ctypes.data
+        elif isinstance(weights, C.Array) and C.sizeof(weights) == self.B * P * C.sizeof(Weights):
+            rows, addr = weights, C.addressof(weights)
+        else:
+            raise HSDDPError(f"weights: a float64 array ({self.B}, {P}, {nf}) or a (Weights * {P}) * {self.B}")
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, dtype=np.int32)
+            if m.shape != (self.B, P):
+                raise HSDDPError(f"mask: shape {m.shape}, expected ({self.B}, {P})")
+        check(lib().hsddp_set_phase_weights(self._h, addr, None if m is None else m.ctypes.data))
+
+    def phase_weights(self):
+        """(rows, is_set): the effective weight rows [B][P][46] (hsddp_get_phase_weights; the fields of
+        hsddp.Weights in order) and the int32 flags [B][P] of those that are overrides."""
+        P = self.P
+        rows = np.zeros((self.B, P, C.sizeof(Weights) // 8))
+        flags = np.zeros((self.B, P), dtype=np.int32)
+        check(lib().hsddp_get_phase_weights(self._h, rows.ctypes.data, flags.ctypes.data))
+        return rows, flags
+
     def set_value_export(self, on: bool = True) -> None:
         """Store G[0], H[0] of every phase in each sweep (SinglePhase::get_value_approx)."""
         check(lib().hsddp_set_value_export(self._h, int(bool(on))))

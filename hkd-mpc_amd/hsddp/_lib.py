@@ -129,6 +129,7 @@ EXPORTS = [
     "hsddp_copy_elements", "hsddp_element_record_bytes", "hsddp_export_elements", "hsddp_import_elements",
     "hsddp_set_terrain", "hsddp_get_terrain",
     "hsddp_set_element_weights", "hsddp_get_element_weights",
+    "hsddp_set_phase_weights", "hsddp_get_phase_weights",
 ]
 
 
@@ -235,6 +236,9 @@ def lib():
     if hasattr(L, "hsddp_set_element_weights"):  # (older A/B builds lack the per-robot weights)
         L.hsddp_set_element_weights.argtypes = [V, C.c_void_p, C.c_void_p]
         L.hsddp_get_element_weights.argtypes = [V, C.c_void_p]
+    if hasattr(L, "hsddp_set_phase_weights"):  # (older A/B builds lack the per-phase weights)
+        L.hsddp_set_phase_weights.argtypes = [V, C.c_void_p, C.c_void_p]
+        L.hsddp_get_phase_weights.argtypes = [V, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

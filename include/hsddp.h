@@ -293,6 +293,43 @@ int hsddp_set_element_weights(hsddp_handle h, const hsddp_hkd_weights *w, const 
 /* The weight rows [B]: with the table off, desc->weights B times.  HSDDP_ERR_ARG: a NULL handle or
  * output, no problem uploaded. */
 int hsddp_get_element_weights(hsddp_handle h, hsddp_hkd_weights *w);
+/* Per-phase cost weights: a row of HKD weights for single phases of single robots.  In the
+ * reference the weights are members of the cost objects, and HKDProblem::create_problem_one_phase
+ * builds one HKDTrackingCost and one HKDFootPlaceReg for every phase (HKDProblem.cpp:243-252): the
+ * phase is the reference's granularity.
+ * w and mask are [B][P] at the phase stride P of hsddp_get_strides.  Phase i of element b with
+ * mask[b][i] != 0 (mask NULL: every phase the element has) takes w[b][i] as its override; entries
+ * past an element's own phases are not read, the other phases keep what they have.  Element b's
+ * phase i reads its override if it has one, else the element's row of hsddp_set_element_weights if
+ * that table is on, else desc->weights.  Everything the phase's CostContainer supplies in the
+ * reference takes the phase's row: the running cost of its knots, the terminal cost at its last
+ * state slot, and their LQ terms (hsddp_download_lq rebuilds lxx and luu from the knot's phase).
+ * w = NULL drops every override: the handle then runs the kernels, arguments and graphs of a handle
+ * that never called this (with per-robot rows present, the per-robot ones).  Negative weights are
+ * legal.  HSDDP_ERR_ARG (the handle unchanged): a NULL handle, no problem uploaded, a non-finite
+ * field in a row that is read.
+ * The call leaves the warm start, the constraint parameters and the stored constraint values alone
+ * and makes the next iteration's LQ pass recompute the slot costs.  It is allowed while inputs are
+ * pending after hsddp_advance(.., x0 = NULL, ..) or hsddp_restart_elements, at the new strides:
+ * advance -> (restart) -> set_phase_weights -> x0 -> solve.
+ * An override belongs to its phase's cost objects and moves as they do.  hsddp_shift,
+ * hsddp_shift_elements and hsddp_advance keep an old phase's override with the phase and drop that
+ * of a removed first phase; a phase they append has none and reads the robot's row, as
+ * create_problem_one_phase constructs new cost objects.  (Terrain differs: an appended phase
+ * repeats the terrain row of the phase before it, the ground under the robot being the same
+ * ground.)  hsddp_restart_elements drops a restarted robot's overrides and keeps its per-robot row.
+ * hsddp_copy_elements, hsddp_export_elements and hsddp_import_elements carry the overrides with the
+ * robot (a record holds them in a block of its own after the header), checked on arrival as
+ * here; a destination without overrides that receives a robot with some takes them up.
+ * hsddp_set_layout and hsddp_set_element_layouts drop them;
+ * hsddp_upload_problem, hsddp_upload_warm_start, hsddp_update_problem* and hsddp_set_options keep
+ * them.  hsddp_set_element_weights on a robot changes what its phases without an override read,
+ * and nothing else.  Call between ticks. */
+int hsddp_set_phase_weights(hsddp_handle h, const hsddp_hkd_weights *w, const int *mask);
+/* The effective rows [B][P] (the element's own row past its phases) and, in is_set [B][P] (may be
+ * NULL), which of them are overrides.  With no override anywhere: what hsddp_get_element_weights
+ * returns, spread over the phases.  HSDDP_ERR_ARG: a NULL handle or w, no problem uploaded. */
+int hsddp_get_phase_weights(hsddp_handle h, hsddp_hkd_weights *w, int *is_set);
 
 /* MultiPhaseDDP::solve (MultiPhaseDDP.cpp:232-428) for every element.  With early exits on, each
  * inner iteration is replayed from a cached hipGraph and stats carries ms_total but no per-phase

@@ -74,9 +74,13 @@ def main():
     ap.add_argument("--weights", action="store_true",
                     help="per-robot cost weights (set_element_weights): every field of each robot's row drawn within "
                          "+-30 %% of the defaults, the whole table set again every tick after the advance")
+    ap.add_argument("--phase-weights", action="store_true",
+                    help="per-phase cost weights (set_phase_weights): every field of each (robot, phase) row drawn "
+                         "within +-30 %% of the defaults; every tick after the advance the table the phases carried on is "
+                         "read back and set again with the phases that entered given rows of their own")
     args = ap.parse_args()
-    if args.host_state + args.measured + args.closed_loop + (args.restart_frac is not None) + args.terrain + args.weights > 1:
-        ap.error("--host-state, --measured, --closed-loop, --restart-frac, --terrain and --weights are separate legs")
+    if args.host_state + args.measured + args.closed_loop + (args.restart_frac is not None) + args.terrain + args.weights + args.phase_weights > 1:
+        ap.error("--host-state, --measured, --closed-loop, --restart-frac, --terrain, --weights and --phase-weights are separate legs")
     B = args.batch
     tab, dt = hsddp.load_quad_reference(os.path.join(ROOT, "tests", "golden", "ref_trot.csv"))
     rng = np.random.default_rng(7)
@@ -104,6 +108,14 @@ def main():
         vals = np.frombuffer(ctypes.string_at(ctypes.addressof(base), 8 * n), np.float64) * rng_w.uniform(0.7, 1.3, (B, n))
         rows = np.ascontiguousarray(vals)  # [B][46]: passed on as it stands
         s.set_element_weights(rows)
+    t_pw, pw_base, rng_p = [], None, np.random.default_rng(19)
+    if args.phase_weights:
+        import ctypes
+        base = hsddp.Weights()
+        hsddp.lib().hsddp_default_weights(ctypes.byref(base))
+        n = ctypes.sizeof(hsddp.Weights) // 8
+        pw_base = np.frombuffer(ctypes.string_at(ctypes.addressof(base), 8 * n), np.float64)
+        s.set_phase_weights(np.ascontiguousarray(pw_base * rng_p.uniform(0.7, 1.3, (B, s.P, n))))  # [B][P][46]
     n_restart = 0
     if restarts and args.restart_frac > 0:
         n_restart = min(B, max(1, int(round(args.restart_frac * B))))
@@ -168,6 +180,18 @@ def main():
             s.set_element_weights(rows)
             t_weights.append(time.perf_counter() - tw)
             s.update_problem(None, xt)
+        elif args.phase_weights:  # advance -> set_phase_weights -> x0 -> solve (the table goes up with the solve's first launch)
+            xt = x0 + rng.uniform(-.01, .01, x0.shape)
+            t0 = time.perf_counter()
+            flags += sum(s.advance(None, 1))
+            tw = time.perf_counter()
+            rows, is_set = s.phase_weights()  # the overrides the phases carried on; a phase that entered has none
+            new = is_set == 0
+            rows[new] = pw_base * rng_p.uniform(0.7, 1.3, (int(new.sum()), rows.shape[2]))
+            rows[it % B, 0, 12] *= 1.0 + 1e-9  # (q_qJ of one phase: an unchanged table is not uploaded again)
+            s.set_phase_weights(rows)
+            t_pw.append(time.perf_counter() - tw)
+            s.update_problem(None, xt)
         else:
             xt = x0 + rng.uniform(-.01, .01, x0.shape)
             t0 = time.perf_counter()
@@ -229,6 +253,11 @@ def main():
         out["metric"] = "MPC tick with per-robot weights (advance + set_element_weights + x0 + solve + extract), HKD trot reference file"
         out["ms_per_tick_median"]["advance"] = med(np.array(t_adv) - np.array(t_weights))
         out["ms_per_tick_median"]["weights"] = med(t_weights)
+    if args.phase_weights:
+        out["metric"] = "MPC tick with per-phase weights (advance + phase_weights + set_phase_weights + x0 + solve + extract), HKD trot reference file"
+        out["ms_per_tick_median"]["advance"] = med(np.array(t_adv) - np.array(t_pw))
+        out["ms_per_tick_median"]["phase_weights"] = med(t_pw)
+        out["phase_weight_overrides"] = int(s.phase_weights()[1].sum())
     if args.terrain:
         out["metric"] = "MPC tick with per-phase terrain (advance + set_terrain + x0 + solve + extract), HKD trot reference file"
         out["ms_per_tick_median"]["advance"] = med(np.array(t_adv) - np.array(t_terrain))
